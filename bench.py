@@ -9,7 +9,10 @@ each rank's frames (dpk_pose_metrics) and one RCCL all-gather of them, 16 B per 
 weak scaling; the north star's only collective).  `value` is whole-job poses/s = frames processed by all ranks / time.
 
 Launch:
-  python bench.py [--gpus N --steps K --warmup W]      N>1: spawns N ranks itself (one process per
+  python bench.py [--gpus N --steps K --warmup W]      the plain run: set up, warm up, time the K steps, print
+                                                         the result line (value, ms_per_step, the roofline of
+                                                         the timed launches, the job's MPJPE from the last step)
+                                                         N>1: spawns N ranks itself (one process per
                                                          GPU, RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* set
                                                          before any HIP call; the parent never touches
                                                          the GPU) and exits non-zero if any rank fails
@@ -18,8 +21,17 @@ Launch:
   python bench.py --gpus 2 --cpu-dry                    launcher/sharding/all-gather rehearsal on CPU
                                                          (gloo, an elementwise stub instead of the
                                                          sampler; no GPU, nothing timed is meaningful)
+  python bench.py --full                                the plain run plus every other leg below that takes
+                                                         runs of its own (cpu_baseline, parity, variants,
+                                                         the all-gather alone, the separately timed reduction)
+  python bench.py --dump-outputs DIR                    after the timed steps, write what the last timed step
+                                                         returned: DIR/poses.npy (float32 [rows, 17, 5], the
+                                                         whole job's rows under a launcher) and
+                                                         DIR/frame_errors.npy (float64 [frames, 2]: MPJPE and
+                                                         P-MPJPE in metres); inputs and weights are seeded, so
+                                                         the same arguments give the same inputs in every run
 
-Also reported on the same JSON line:
+Also reported on the same JSON line (cpu_baseline, parity and variants only with --full):
   roofline      the sampler kernel's algorithmic FLOP rate (25,996,254 FLOP per
                 pose-step × poses × K ÷ its average launch duration, measured with HIP events
                 around that kernel on the stream it is launched on) vs the fp32 MFMA peak;
@@ -97,15 +109,24 @@ def parse(argv=None):
     ap.add_argument("--cpu-threads", type=str, default=None,
                     help="comma-separated thread counts for the CPU baseline legs (default: the box's CPU share, "
                          "OMP_NUM_THREADS, or every physical core of this process's affinity when unset)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: CPU baseline and parity, the other GEMM modes and "
+                         "config 3 (variants), the all-gather timed alone, the reassembly check, the separately timed "
+                         "final reduction and the warm schedule build (setup_ms)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last timed step's outputs as DIR/poses.npy (float32) and "
+                         "DIR/frame_errors.npy (float64), at most 64 MB in all (a fixed seeded sample of rows beyond that)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline and parity legs")
     ap.add_argument("--gemm", choices=("fp32", "f16x3", "bf16"), default=None,
                     help="per-layer GEMM arithmetic of the headline (dpk_set_gemm_mode); fp32 is the reference's")
     ap.add_argument("--no-variants", dest="variants", action="store_false",
-                    help="skip timing the other GEMM mode (reported under 'variants')")
+                    help="with --full: skip timing the other GEMM modes (reported under 'variants')")
     ap.add_argument("--cpu-dry", action="store_true",
                     help="rehearse the multi-rank launch, sharding and all-gather on CPU (gloo) with an "
                          "elementwise stub in place of the HIP sampler")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     preset = CONFIGS[args.config]
     for k in ("hyp", "K", "T_test", "T", "gemm", "graph"):
         if getattr(args, k) is None:
@@ -291,6 +312,34 @@ def config3_parity(args, x_all, tgt_all, out_bf16, out_fp32):
     return res
 
 
+DUMP_CAP_BYTES = 60_000_000    # --dump-outputs: all arrays together (under 64 MB with the .npy headers)
+
+
+def dump_outputs(path, out, fe, n_frames, hyp, use_dist, rank):
+    """--dump-outputs: what the last timed step handed back, as .npy files written by rank 0.
+    poses.npy: the final poses, float32 [hyp * frames, 17, 5] in the reference's hypothesis-major row order
+    (under a launcher the shards of all ranks, reassembled by one more all-gather, so every rank calls this);
+    frame_errors.npy: the step's per-frame (MPJPE, P-MPJPE) in metres, float64 [frames, 2], already gathered.
+    An array over its share of DUMP_CAP_BYTES is cut to a fixed, seeded, sorted sample of its rows."""
+    import numpy as np
+    import torch
+
+    from diffpose_amd import dist as D
+
+    poses = D.gather_frames(out, n_frames, hyp) if use_dist else out
+    if rank != 0:
+        return
+    os.makedirs(path, exist_ok=True)
+    for name, t, dtype, cap in (("poses", poses, np.float32, DUMP_CAP_BYTES - 4_000_000),
+                                ("frame_errors", fe, np.float64, 4_000_000)):
+        row_bytes = max(1, t[0].numel() * np.dtype(dtype).itemsize) if t.shape[0] else 1
+        keep = cap // row_bytes
+        if t.shape[0] > keep:
+            idx = np.sort(np.random.default_rng(0).choice(t.shape[0], size=keep, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(t.detach().cpu().numpy().astype(dtype, copy=False)))
+
+
 # ---------------------------------------------------------------------------------------------
 # one rank
 # ---------------------------------------------------------------------------------------------
@@ -352,12 +401,14 @@ def rank_main(args):
         # host-synchronous: the call returns with the schedule built.  The first build in a process also
         # pays the code-object load and first launch of temb_kernel (setup_cold_ms); the schedule the
         # timed steps use is built second, warm (setup_ms: what a caller pays per new schedule)
+        # (--full; a plain run builds the timed steps' schedule once, cold)
         t_set = time.perf_counter()
-        model.set_schedule(seq, betas, args.eta + 0.5)
+        model.set_schedule(seq, betas, args.eta + 0.5 if args.full else args.eta)
         setup_cold_ms = (time.perf_counter() - t_set) * 1e3
-        t_set = time.perf_counter()
-        model.set_schedule(seq, betas, args.eta)
-        setup_ms = (time.perf_counter() - t_set) * 1e3
+        if args.full:
+            t_set = time.perf_counter()
+            model.set_schedule(seq, betas, args.eta)
+            setup_ms = (time.perf_counter() - t_set) * 1e3
 
     gathered = {}
     tg_local = torch.from_numpy(tgt_all[lo:hi]).to(dev)
@@ -461,11 +512,14 @@ def rank_main(args):
     per_rank_ms = [mine / args.steps * 1e3]
     allgather_ms = None
     reassembly = None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, gathered["fe"], B_total, args.hyp, use_dist, rank)
     if use_dist:
         t = torch.tensor([mine / args.steps * 1e3], dtype=torch.float64, device=dev)
         lst = [torch.zeros_like(t) for _ in range(world)]
         dist.all_gather(lst, t)
         per_rank_ms = [round(float(v.item()), 4) for v in lst]
+    if use_dist and args.full:
         # the step's all-gather alone (per-frame errors, 16 B per frame), same barrier/sync bracket, max over ranks
         fe_local = frame_errors(out)
         dist.barrier()
@@ -490,38 +544,42 @@ def rank_main(args):
     # ---- the final MPJPE reduction (runners/diffpose_frame.py:382-387): per-frame (MPJPE, P-MPJPE) of this
     #      rank's frames (dpk_pose_metrics: hypothesis mean, root-relative, Procrustes, fp64), then one
     #      all-gather of those 16 B per frame; every rank ends with the job's MPJPE.  Once, after the timed steps.
-    frame_errors(out)      # untimed first (first launches in this process: the metrics kernel, torch's cat)
-    if use_dist:
-        dist.barrier()
-    sync()
-    t0 = time.perf_counter()
-    fe = frame_errors(out)
-    if use_dist:
-        fe = D.gather_frames(fe, B_total, 1)
-    sync()
-    reduce_s = time.perf_counter() - t0
-    # the timed steps' own reduction of the same output gave the same numbers
-    g = gathered["fe"]
-    eq = bool(((fe == g) | (torch.isnan(fe) & torch.isnan(g))).all())      # the dry stub's P-MPJPE is NaN
-    same = torch.tensor([1 if eq else 0], dtype=torch.int32, device=dev)
-    if use_dist:
-        dist.all_reduce(same, op=dist.ReduceOp.MIN)
-    if use_dist:
-        reduce_s = D.max_over_ranks(reduce_s, device=dev)
+    #      A plain run reports the last timed step's own reduction; --full repeats and times it alone.
+    fe = gathered["fe"]
+    reduce_s = None
+    if args.full:
+        frame_errors(out)      # untimed first (first launches in this process: the metrics kernel, torch's cat)
+        if use_dist:
+            dist.barrier()
+        sync()
+        t0 = time.perf_counter()
+        fe = frame_errors(out)
+        if use_dist:
+            fe = D.gather_frames(fe, B_total, 1)
+        sync()
+        reduce_s = time.perf_counter() - t0
+        # the timed steps' own reduction of the same output gave the same numbers
+        g = gathered["fe"]
+        eq = bool(((fe == g) | (torch.isnan(fe) & torch.isnan(g))).all())      # the dry stub's P-MPJPE is NaN
+        same = torch.tensor([1 if eq else 0], dtype=torch.int32, device=dev)
+        if use_dist:
+            dist.all_reduce(same, op=dist.ReduceOp.MIN)
+        if use_dist:
+            reduce_s = D.max_over_ranks(reduce_s, device=dev)
+        if not bool(same.item()):
+            print("bench: the steps' gathered per-frame errors differ from the final reduction's", file=sys.stderr)
+            return 3
     fe_h = fe.cpu().numpy()
-    if not bool(same.item()):
-        print("bench: the steps' gathered per-frame errors differ from the final reduction's", file=sys.stderr)
-        return 3
     mpjpe_line = {"p1_mm": round(float(fe_h[:, 0].mean()) * 1000.0, 6),
                   "p2_mm": None if dry else round(float(fe_h[:, 1].mean()) * 1000.0, 6),
-                  "frames": int(fe_h.shape[0]), "reduce_ms": round(reduce_s * 1e3, 4),
+                  "frames": int(fe_h.shape[0]), "reduce_ms": None if reduce_s is None else round(reduce_s * 1e3, 4),
                   "how": ("per-frame (MPJPE, P-MPJPE) on each rank's frames (dpk_pose_metrics, fp64), " +
                           ("one all_gather of 16 B per frame, inside every timed step" if use_dist
                            else "one rank, no collective; inside every timed step (the same work as at N>1)")),
                   "targets": "synthetic (seeded), root-relative"}
-    out_main = out.detach().cpu().numpy() if (world == 1 and rank == 0 and not dry) else None
+    out_main = out.detach().cpu().numpy() if (args.full and world == 1 and rank == 0 and not dry) else None
     variants = {}
-    if args.variants and not dry:
+    if args.full and args.variants and not dry:
         for g in ("fp32", "f16x3"):
             if g == args.gemm:
                 continue
@@ -576,12 +634,12 @@ def rank_main(args):
         "per_rank_ms": per_rank_ms,
         "setup_ms": None if setup_ms is None else round(setup_ms, 4),
         "setup_cold_ms": None if setup_cold_ms is None else round(setup_cold_ms, 4),
-        "setup_note": None if setup_ms is None else (
+        "setup_note": None if setup_cold_ms is None else (
             f"per (weights, schedule), outside the timed region: dpk_set_schedule's host step scalars, upload and "
             f"temb_kernel ({K} workgroups: the timestep MLP and the 5 temb_proj rows of every step, batch-invariant, "
             f"SURVEY a7), host-synchronous wall time; every dpk_sample with that schedule reuses them, so a caller "
             f"running a single batch pays it once on top of ms_per_step; setup_cold_ms is the process's first build "
-            f"(adds the code-object load and first launch)"),
+            f"(adds the code-object load and first launch); setup_ms, a second, warm build, is measured with --full"),
         "roofline": roof,
         "cpu_baseline": None,
     }
@@ -599,7 +657,7 @@ def rank_main(args):
         result["rows_per_s"] = round(value * args.hyp, 2)
 
     # ---- CPU baseline + parity (rank 0, N=1) ----
-    if world == 1 and rank == 0 and not args.no_cpu and not dry:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu and not dry:
         cb, ref_np, n_cpu = cpu_baseline(args, x_all, seq, betas, K, args.hyp)
         result["cpu_baseline"] = cb
         if args.eta == 0.0 and ref_np is not None:

@@ -7,7 +7,7 @@ shift
 EXTRA="$*"
 O=$R/gpurun_out
 mkdir -p $O
-timeout -k 10 400 python3 $R/bench.py $EXTRA > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || exit 1
+timeout -k 10 400 python3 $R/bench.py --full $EXTRA > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || exit 1
 cut -c1-300 $O/${TAG}_bench.json
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_prof -o run -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu --no-variants $EXTRA > $O/${TAG}_bench_under_rocprof.json 2>$O/${TAG}_prof.err || exit 2
