@@ -611,9 +611,6 @@ __global__ void __launch_bounds__(256) pose_out(const float* __restrict__ x2d, c
 
 // ---------------------------------------------------------------------------------------
 // Host side of the generic path
-struct GenLayer {
-    size_t wqkv, bqkv, wo, bo, n0a, n0b, n1a, n1b, w1, b1, w2, b2, lg, wc1, bc1, wc2, bc2;
-};
 struct GenScratch {
     hipStream_t st = nullptr;
     float* p = nullptr;
@@ -652,27 +649,21 @@ struct GenPack {
 // dpkw, 2-pose tiles), hid 128 / 4 heads (dpkw4), hid 64 / 2 heads (dpkn, 4-pose tiles) or hid 64 / 4 heads
 // (dpkn4), 17 joints, num_layer <= 5, coords 5 -> 5,
 // fp32 GEMMs, runs that instance's sample_kernel — the same fused K-step loop as the shipped shape —
-// instead of the per-op launches below; its arena is packed on the host from the generic staging arena
-// (dpk_genfused.inc).  DPK_GEN_FUSED=0 keeps such a handle on the per-op path (A/B; tests compare the two).
+// instead of the per-op launches below; its arena is packed on the host from the staging by the instance's
+// pack_model (dpk_pack.inc).  DPK_GEN_FUSED=0 keeps such a handle on the per-op path (A/B; tests compare the two).
 struct GenFused {
     int inst = 0;                // index into the instance list below (gen_new: the first that fits)
-    std::vector<float> ha, ht;   // host staging: packed arena, timestep-MLP arena (the instance's layouts)
+    Packed pk;                   // the instance's arenas (its pack_model), no half-width copies
     float* arena = nullptr;
     float* temb = nullptr;
-    bool sparse = false;         // the adjacency fits the H36M Chebyshev pattern (sparse kernels)
 };
 
 struct GenModel {
-    int D = 0, H = 0, J = 0, L = 0, cin = 0, cout = 0, kind = 0, E = 0;
+    Stage s;                   // host staging of the weights and the graph; `dev` is its device copy
     GenFused* fz = nullptr;    // non-null: the fused wide-model sampler serves dpk_sample / dpk_eps
     std::vector<GenPack> packs;
     std::vector<float> hp;     // host staging of the packed arena
     float* devp = nullptr;     // device packed arena
-    std::vector<GenLayer> lay;
-    size_t win = 0, bin = 0, wout = 0, bout = 0, t1 = 0, t2 = 0, d0w = 0, d0b = 0, d1w = 0, d1b = 0;
-    size_t wtp = 0, btp = 0;   // every layer's temb_proj: [L][E][D] (k-major), [L][D]
-    size_t floats = 0;
-    std::vector<float> h;      // host staging of the arena
     float* dev = nullptr;      // device arena
     std::vector<GenScratch> scratch;
     GenScratch spare;          // for the next capture (CapRes::gen): sized by uncaptured calls, never launched on
@@ -690,18 +681,6 @@ static void gen_drop_graphs(GenModel* g, const float* scratch) {   // scratch nu
     g->graphs.swap(keep);
 }
 
-namespace dpkw {
-#include "dpk_genfused.inc"
-}  // namespace dpkw
-namespace dpkw4 {
-#include "dpk_genfused.inc"
-}  // namespace dpkw4
-namespace dpkn {
-#include "dpk_genfused.inc"
-}  // namespace dpkn
-namespace dpkn4 {
-#include "dpk_genfused.inc"
-}  // namespace dpkn4
 // the instance serving a GenFused handle (GenFused::inst): 0 dpkw, 1 dpkw4, 2 dpkn, 3 dpkn4
 #define DPK_FZ_SWITCH(INST, CALL)          \
     switch (INST) {                        \
@@ -717,10 +696,10 @@ static int gen_fused_pick(int D, int H, int J, int L, int cin, int cout, int kin
     if (dpkn4::fused_fits(D, H, J, L, cin, cout, kind)) return 3;
     return -1;
 }
-static void gen_fused_pack(GenModel* g) { DPK_FZ_SWITCH(g->fz->inst, fused_pack(g)) }
+static void gen_fused_pack(GenModel* g) { DPK_FZ_SWITCH(g->fz->inst, pack_model(g->s, g->fz->pk, false)) }
 template <int MODE>
 static void gen_fused_launch(GenModel* g, const SampleArgs& a, hipStream_t st) {
-    DPK_FZ_SWITCH(g->fz->inst, template fused_launch<MODE>(g, a, st))
+    DPK_FZ_SWITCH(g->fz->inst, template fused_launch<MODE>(g->fz->pk.sparse, g->fz->arena, a, st))
 }
 static void gen_fused_temb(const GenFused* f, const float* t, int stride, int count, float* out, hipStream_t st) {
     DPK_FZ_SWITCH(f->inst, fused_temb(f->temb, t, stride, count, out, st))
@@ -736,27 +715,7 @@ static size_t gen_fused_tp(const GenFused* f) {
 
 static GenModel* gen_new(int D, int H, int J, int L, int cin, int cout, int kind) {
     GenModel* g = new GenModel();
-    g->D = D, g->H = H, g->J = J, g->L = L, g->cin = cin, g->cout = cout, g->kind = kind, g->E = 4 * D;
-    size_t o = 0;
-    auto take = [&](size_t n) {
-        const size_t at = o;
-        o += (n + 3) / 4 * 4;
-        return at;
-    };
-    g->lay.resize(L);
-    for (auto& l : g->lay) {
-        l.wqkv = take((size_t)D * 3 * D), l.bqkv = take(3 * D), l.wo = take((size_t)D * D), l.bo = take(D);
-        l.n0a = take(D), l.n0b = take(D), l.n1a = take(D), l.n1b = take(D);
-        l.w1 = take((size_t)D * 2 * D), l.b1 = take(2 * D), l.w2 = take((size_t)2 * D * D), l.b2 = take(D);
-        l.lg = take((size_t)J * J), l.wc1 = take((size_t)3 * D * D), l.bc1 = take(D), l.wc2 = take((size_t)3 * D * D);
-        l.bc2 = take(D);
-    }
-    g->win = take((size_t)3 * cin * D), g->bin = take(D), g->wout = take((size_t)3 * D * cout), g->bout = take(cout);
-    g->t1 = take((size_t)J * J), g->t2 = take((size_t)J * J);
-    g->d0w = take((size_t)D * g->E), g->d0b = take(g->E), g->d1w = take((size_t)g->E * g->E), g->d1b = take(g->E);
-    g->wtp = take((size_t)L * g->E * D), g->btp = take((size_t)L * D);
-    g->floats = o;
-    g->h.assign(o, 0.f);
+    stage_init(g->s, D, H, J, L, cin, cout, kind);
     const char* fe = getenv("DPK_GEN_FUSED");
     const int inst = (fe && atoi(fe) == 0) ? -1 : gen_fused_pick(D, H, J, L, cin, cout, kind);
     if (inst >= 0) {
@@ -797,16 +756,16 @@ static void gen_pack(GenModel* g) {
         g->packs.push_back(GenPack{w, off, K, N, NJ});
         off += (size_t)((K + 15) / 16) * NTp * 256;
     };
-    const int D = g->D;
-    for (const GenLayer& o : g->lay) {
+    const int D = g->s.D;
+    for (const GenLayer& o : g->s.lay) {
         add(o.wqkv, D, 3 * D), add(o.wo, D, D), add(o.w1, D, 2 * D), add(o.w2, 2 * D, D);
         add(o.wc1, 3 * D, D), add(o.wc2, 3 * D, D);
     }
-    add(g->win, 3 * g->cin, D);
+    add(g->s.win, 3 * g->s.cin, D);
     g->hp.assign(off, 0.f);
     for (const GenPack& p : g->packs) {
         const int KC = (p.K + 15) / 16, NT16 = (p.N + 15) / 16, NTp = (NT16 + p.NJ - 1) / p.NJ * p.NJ;
-        const float* W = g->h.data() + p.w;
+        const float* W = g->s.h.data() + p.w;
         float* dst = g->hp.data() + p.off;
         for (int c = 0; c < KC; ++c)
             for (int t = 0; t < NT16; ++t)
@@ -824,129 +783,17 @@ static int gen_upload(dpk_handle* h, GenModel* g) {
     if (g->fz) {
         gen_fused_pack(g);
         GenFused* f = g->fz;
-        if (!f->arena) HIPCHK(h, hipMalloc(&f->arena, f->ha.size() * 4));
-        if (!f->temb) HIPCHK(h, hipMalloc(&f->temb, f->ht.size() * 4));
-        HIPCHK(h, hipMemcpy(f->arena, f->ha.data(), f->ha.size() * 4, hipMemcpyHostToDevice));
-        HIPCHK(h, hipMemcpy(f->temb, f->ht.data(), f->ht.size() * 4, hipMemcpyHostToDevice));
+        if (!f->arena) HIPCHK(h, hipMalloc(&f->arena, f->pk.arena.size() * 4));
+        if (!f->temb) HIPCHK(h, hipMalloc(&f->temb, f->pk.temb.size() * 4));
+        HIPCHK(h, hipMemcpy(f->arena, f->pk.arena.data(), f->pk.arena.size() * 4, hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(f->temb, f->pk.temb.data(), f->pk.temb.size() * 4, hipMemcpyHostToDevice));
     }
-    if (!g->dev) HIPCHK(h, hipMalloc(&g->dev, g->floats * 4));
-    HIPCHK(h, hipMemcpy(g->dev, g->h.data(), g->floats * 4, hipMemcpyHostToDevice));
+    if (!g->dev) HIPCHK(h, hipMalloc(&g->dev, g->s.floats * 4));
+    HIPCHK(h, hipMemcpy(g->dev, g->s.h.data(), g->s.floats * 4, hipMemcpyHostToDevice));
     gen_pack(g);
     if (!g->devp && !g->hp.empty()) HIPCHK(h, hipMalloc(&g->devp, g->hp.size() * 4));
     if (!g->hp.empty()) HIPCHK(h, hipMemcpy(g->devp, g->hp.data(), g->hp.size() * 4, hipMemcpyHostToDevice));
     return DPK_OK;
-}
-
-// Chebyshev terms T1 = L, T2 = 2 L L - I of the normalised Laplacian for any n_pts (as cheb_terms)
-static void gen_set_graph(GenModel* g, const float* adj) {
-    const int J = g->J;
-    std::vector<float> d(J), L((size_t)J * J);
-    for (int i = 0; i < J; ++i) {
-        float s = 0.f;
-        for (int j = 0; j < J; ++j) s += adj[i * J + j];
-        d[i] = 1.0f / sqrtf(s);
-    }
-    for (int i = 0; i < J; ++i)
-        for (int j = 0; j < J; ++j) L[i * J + j] = (i == j ? 1.f : 0.f) - (d[i] * adj[i * J + j]) * d[j];
-    for (int i = 0; i < J; ++i)
-        for (int j = 0; j < J; ++j) {
-            float acc = 0.f;
-            for (int k = 0; k < J; ++k) acc += L[i * J + k] * L[k * J + j];
-            g->h[g->t1 + i * J + j] = L[i * J + j];
-            g->h[g->t2 + i * J + j] = 2.f * acc - (i == j ? 1.f : 0.f);
-        }
-}
-
-// Weights from the state_dict (keys and sizes of models/gcndiff.py / gcnpose.py for this shape);
-// nn.Linear (out, in) and ChebConv (3, 1, in, out) weights stored k-major [in][out]
-template <class Get>
-static bool gen_load(GenModel* g, Get&& get) {
-    const int D = g->D, E = g->E, J = g->J;
-    float* A = g->h.data();
-    for (int l = 0; l < g->L; ++l) {
-        const GenLayer& o = g->lay[l];
-        const std::string at = "atten_layers." + std::to_string(l) + ".", gc = "gconv_layers." + std::to_string(l) + ".";
-        const float* w[4];
-        const float* b[4];
-        for (int j = 0; j < 4; ++j) {
-            w[j] = get(at + "self_attn.linears." + std::to_string(j) + ".weight", (int64_t)D * D);
-            b[j] = get(at + "self_attn.linears." + std::to_string(j) + ".bias", (int64_t)D);
-            if (!w[j] || !b[j]) return false;
-        }
-        const float* ahat = get(at + "feed_forward.A_hat", (int64_t)J * J);
-        const float* f1w = get(at + "feed_forward.gconv1.fc.weight", (int64_t)2 * D * D);
-        const float* f1b = get(at + "feed_forward.gconv1.fc.bias", (int64_t)2 * D);
-        const float* f2w = get(at + "feed_forward.gconv2.fc.weight", (int64_t)2 * D * D);
-        const float* f2b = get(at + "feed_forward.gconv2.fc.bias", (int64_t)D);
-        const float* n0a = get(at + "sublayer.0.norm.a_2", D);
-        const float* n0b = get(at + "sublayer.0.norm.b_2", D);
-        const float* n1a = get(at + "sublayer.1.norm.a_2", D);
-        const float* n1b = get(at + "sublayer.1.norm.b_2", D);
-        const float* c1w = get(gc + "gconv1.gconv.weight", (int64_t)3 * D * D);
-        const float* c1b = get(gc + "gconv1.gconv.bias", D);
-        const float* c2w = get(gc + "gconv2.gconv.weight", (int64_t)3 * D * D);
-        const float* c2b = get(gc + "gconv2.gconv.bias", D);
-        if (!ahat || !f1w || !f1b || !f2w || !f2b || !n0a || !n0b || !n1a || !n1b || !c1w || !c1b || !c2w || !c2b)
-            return false;
-        for (int k = 0; k < D; ++k)
-            for (int n = 0; n < 3 * D; ++n) A[o.wqkv + (size_t)k * 3 * D + n] = w[n / D][(size_t)(n % D) * D + k];
-        for (int n = 0; n < 3 * D; ++n) A[o.bqkv + n] = b[n / D][n % D];
-        for (int k = 0; k < D; ++k)
-            for (int n = 0; n < D; ++n) A[o.wo + (size_t)k * D + n] = w[3][(size_t)n * D + k];
-        for (int k = 0; k < D; ++k)
-            for (int n = 0; n < 2 * D; ++n) A[o.w1 + (size_t)k * 2 * D + n] = f1w[(size_t)n * D + k];
-        for (int k = 0; k < 2 * D; ++k)
-            for (int n = 0; n < D; ++n) A[o.w2 + (size_t)k * D + n] = f2w[(size_t)n * 2 * D + k];
-        for (size_t i = 0; i < (size_t)3 * D * D; ++i) {   // (3,1,in,out) is already [3*in][out]
-            A[o.wc1 + i] = c1w[i];
-            A[o.wc2 + i] = c2w[i];
-        }
-        for (int c = 0; c < D; ++c) {
-            A[o.bo + c] = b[3][c], A[o.b2 + c] = f2b[c], A[o.bc1 + c] = c1b[c], A[o.bc2 + c] = c2b[c];
-            A[o.n0a + c] = n0a[c], A[o.n0b + c] = n0b[c], A[o.n1a + c] = n1a[c], A[o.n1b + c] = n1b[c];
-        }
-        for (int c = 0; c < 2 * D; ++c) A[o.b1 + c] = f1b[c];
-        // GraphNet Laplacian (GraFormer.py:174-178): column sums + 1e-5
-        std::vector<float> dh(J);
-        for (int k = 0; k < J; ++k) {
-            float s = 0.f;
-            for (int i = 0; i < J; ++i) s += ahat[i * J + k];
-            dh[k] = 1.0f / sqrtf(s + 1e-5f);
-        }
-        for (int i = 0; i < J; ++i)
-            for (int j = 0; j < J; ++j) A[o.lg + i * J + j] = (dh[i] * ahat[i * J + j]) * dh[j];
-        if (g->kind == 0) {
-            const float* tpw = get(gc + "temb_proj.weight", (int64_t)D * E);
-            const float* tpb = get(gc + "temb_proj.bias", D);
-            if (!tpw || !tpb) return false;
-            for (int k = 0; k < E; ++k)
-                for (int n = 0; n < D; ++n) A[g->wtp + ((size_t)l * E + k) * D + n] = tpw[(size_t)n * E + k];
-            for (int c = 0; c < D; ++c) A[g->btp + (size_t)l * D + c] = tpb[c];
-        }
-    }
-    const float* wi = get("gconv_input.weight", (int64_t)3 * g->cin * D);
-    const float* bi = get("gconv_input.bias", D);
-    const float* wout = get("gconv_output.weight", (int64_t)3 * D * g->cout);
-    const float* bout = get("gconv_output.bias", g->cout);
-    if (!wi || !bi || !wout || !bout) return false;
-    std::copy(wi, wi + (size_t)3 * g->cin * D, A + g->win);
-    std::copy(bi, bi + D, A + g->bin);
-    std::copy(wout, wout + (size_t)3 * D * g->cout, A + g->wout);
-    std::copy(bout, bout + g->cout, A + g->bout);
-    if (g->kind == 0) {
-        const float* d0w = get("temb.dense.0.weight", (int64_t)E * D);
-        const float* d0b = get("temb.dense.0.bias", E);
-        const float* d1w = get("temb.dense.1.weight", (int64_t)E * E);
-        const float* d1b = get("temb.dense.1.bias", E);
-        if (!d0w || !d0b || !d1w || !d1b) return false;
-        for (int k = 0; k < D; ++k)
-            for (int o = 0; o < E; ++o) A[g->d0w + (size_t)k * E + o] = d0w[(size_t)o * D + k];
-        for (int k = 0; k < E; ++k)
-            for (int o = 0; o < E; ++o) A[g->d1w + (size_t)k * E + o] = d1w[(size_t)o * E + k];
-        std::copy(d0b, d0b + E, A + g->d0b);
-        std::copy(d1b, d1b + E, A + g->d1b);
-    }
-    return true;
 }
 
 // Per-stream scratch of at least n floats (grown after a sync of that stream only: launches on
@@ -1039,10 +886,10 @@ static inline unsigned gen_blocks(long long n) { return (unsigned)((n + 255) / 2
 
 // floats of activation scratch for N poses (gen_forward's buffers)
 static size_t gen_act_floats(const GenModel* g, int N) {
-    const size_t M = (size_t)N * g->J, D = g->D;
+    const size_t M = (size_t)N * g->s.J, D = g->s.D;
     // Zs holds a Chebyshev operand [X | T1X | T2X] of the hidden width or of the input (3 * cin)
-    const size_t Z = 3 * std::max(D, (size_t)g->cin);
-    return M * (D + D + Z + D + 2 * D + 2 * D) + M * (size_t)std::max(g->cout, 4);
+    const size_t Z = 3 * std::max(D, (size_t)g->s.cin);
+    return M * (D + D + Z + D + 2 * D + 2 * D) + M * (size_t)std::max(g->s.cout, 4);
 }
 
 // One GCNdiff / GCNpose forward of N poses x (N, J, cin) -> y (N, J, cout).  tp: per-layer timestep
@@ -1050,12 +897,12 @@ static size_t gen_act_floats(const GenModel* g, int N) {
 // GCNpose.  S: gen_act_floats(N) floats of scratch.
 static void gen_forward(GenModel* g, hipStream_t st, const float* x, int N, const float* tp, int tp_stride,
                         unsigned mask, const unsigned* pmask, float* y, float* S, int n_cu) {
-    const int D = g->D, J = g->J, M = N * J;
+    const int D = g->s.D, J = g->s.J, M = N * J;
     const float* W = g->dev;
     float* Hs = S;
     float* Ys = Hs + (size_t)M * D;
     float* Zs = Ys + (size_t)M * D;
-    float* As = Zs + (size_t)M * 3 * std::max(D, g->cin);
+    float* As = Zs + (size_t)M * 3 * std::max(D, g->s.cin);
     float* Fs = As + (size_t)M * D;
     float* Gs = Fs + (size_t)M * 2 * D;
     // DPK_GEN_GEMM=lds: the LDS-staged gemm<BM> everywhere (A/B)
@@ -1112,11 +959,11 @@ static void gen_forward(GenModel* g, hipStream_t st, const float* x, int N, cons
     auto cheb = [&](const float* xin, int C) {
         const size_t lds = ((size_t)J * C + 2 * J * J) * 4;
         if (lds <= 65536)
-            hipLaunchKernelGGL(dpkg::cheb_basis<true>, dim3((unsigned)N), dim3(256), lds, st, W + g->t1, W + g->t2, xin,
+            hipLaunchKernelGGL(dpkg::cheb_basis<true>, dim3((unsigned)N), dim3(256), lds, st, W + g->s.t1, W + g->s.t2, xin,
                                Zs, N, J, C);
         else
-            hipLaunchKernelGGL(dpkg::cheb_basis<false>, dim3(gen_blocks((long long)M * C)), dim3(256), 0, st, W + g->t1,
-                               W + g->t2, xin, Zs, N, J, C);
+            hipLaunchKernelGGL(dpkg::cheb_basis<false>, dim3(gen_blocks((long long)M * C)), dim3(256), 0, st, W + g->s.t1,
+                               W + g->s.t2, xin, Zs, N, J, C);
     };
     auto graph = [&](size_t lg, const float* xin, int C, float* yout) {
         const size_t lds = ((size_t)J * C + J * J) * 4;
@@ -1126,27 +973,27 @@ static void gen_forward(GenModel* g, hipStream_t st, const float* x, int N, cons
             hipLaunchKernelGGL(dpkg::graph<false>, dim3(gen_blocks((long long)M * C)), dim3(256), 0, st, W + lg, xin, C,
                                yout, C, N, J, C);
     };
-    cheb(x, g->cin);
-    gemm(Zs, 3 * g->cin, g->win, g->bin, Hs, D, D, dpkg::G_BIAS);
-    for (int l = 0; l < g->L; ++l) {
-        const GenLayer& o = g->lay[l];
+    cheb(x, g->s.cin);
+    gemm(Zs, 3 * g->s.cin, g->s.win, g->s.bin, Hs, D, D, dpkg::G_BIAS);
+    for (int l = 0; l < g->s.L; ++l) {
+        const GenLayer& o = g->s.lay[l];
         hipLaunchKernelGGL(dpkg::layer_norm, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, Hs, Ys, M, D, W + o.n0a,
                            W + o.n0b);
         gemm(Ys, D, o.wqkv, o.bqkv, Zs, 3 * D, 3 * D, dpkg::G_BIAS);
         // poses per workgroup: enough (head, query) threads to fill 256, within 64 KB of LDS
-        const bool avec = (D / g->H) % 4 == 0 && D % 8 == 0;
+        const bool avec = (D / g->s.H) % 4 == 0 && D % 8 == 0;
         const size_t pose_bytes = (size_t)J * (3 * D + (avec ? 4 : 1)) * 4;
-        const int ppb = std::max(1, std::min(256 / (g->H * J), (int)(65536 / pose_bytes)));
+        const int ppb = std::max(1, std::min(256 / (g->s.H * J), (int)(65536 / pose_bytes)));
         const unsigned ab = (unsigned)((N + ppb - 1) / ppb);
         if (pose_bytes > 65536)
             hipLaunchKernelGGL((dpkg::attention<false, false>), dim3((unsigned)N), dim3(256), 0, st, Zs, As, N, J, D,
-                               g->H, mask, pmask, 1);
+                               g->s.H, mask, pmask, 1);
         else if (avec)
             hipLaunchKernelGGL((dpkg::attention<true, true>), dim3(ab), dim3(256), pose_bytes * ppb, st, Zs, As, N, J, D,
-                               g->H, mask, pmask, ppb);
+                               g->s.H, mask, pmask, ppb);
         else
             hipLaunchKernelGGL((dpkg::attention<true, false>), dim3(ab), dim3(256), pose_bytes * ppb, st, Zs, As, N, J,
-                               D, g->H, mask, pmask, ppb);
+                               D, g->s.H, mask, pmask, ppb);
         gemm(As, D, o.wo, o.bo, Hs, D, D, dpkg::G_RESID);
         hipLaunchKernelGGL(dpkg::layer_norm, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, Hs, Ys, M, D, W + o.n1a,
                            W + o.n1b);
@@ -1161,17 +1008,17 @@ static void gen_forward(GenModel* g, hipStream_t st, const float* x, int N, cons
         gemm(Zs, 3 * D, o.wc2, o.bc2, Hs, D, D, dpkg::G_RESID_RELU);
     }
     cheb(Hs, D);
-    gemm(Zs, 3 * D, g->wout, g->bout, y, g->cout, g->cout, dpkg::G_BIAS);
+    gemm(Zs, 3 * D, g->s.wout, g->s.bout, y, g->s.cout, g->s.cout, dpkg::G_BIAS);
 }
 
 // timestep projections of `count` t values (stride tstride) into tproj [count][L][D]
 static void gen_temb(GenModel* g, hipStream_t st, const float* tvals, int tstride, int count, float* tproj) {
     const float* W = g->dev;
-    const int half = g->D / 2;
+    const int half = g->s.D / 2;
     const float neg = -(float)(log(10000.0) / (double)(half - 1));
-    const size_t lds = (size_t)(g->D + 2 * g->E) * 4;
-    hipLaunchKernelGGL(dpkg::temb, dim3((unsigned)count), dim3(256), lds, st, W + g->d0w, W + g->d0b, W + g->d1w,
-                       W + g->d1b, W + g->wtp, W + g->btp, tvals, tstride, g->D, g->E, g->L, neg, tproj);
+    const size_t lds = (size_t)(g->s.D + 2 * g->s.E) * 4;
+    hipLaunchKernelGGL(dpkg::temb, dim3((unsigned)count), dim3(256), lds, st, W + g->s.d0w, W + g->s.d0b, W + g->s.d1w,
+                       W + g->s.d1b, W + g->s.wtp, W + g->s.btp, tvals, tstride, g->s.D, g->s.E, g->s.L, neg, tproj);
 }
 
 static int gen_fused_sample(dpk_handle* h, Sched* sc, const float* x, float* out, float* xs, float* x0s, int N,
@@ -1179,7 +1026,7 @@ static int gen_fused_sample(dpk_handle* h, Sched* sc, const float* x, float* out
     GenModel* g = h->gen;
     GenFused* f = g->fz;
     const int K = sc->K;
-    const long long n = (long long)N * g->J * g->cin;
+    const long long n = (long long)N * g->s.J * g->s.cin;
     float* S = nullptr;          // the schedule's timestep projections [K][NL][D], per call
     int rc = gen_scratch_any(h, g, st, cap, (size_t)K * gen_fused_tp(f), &S, "dpk_sample");
     if (rc) return rc;
@@ -1199,7 +1046,7 @@ static int gen_fused_sample(dpk_handle* h, Sched* sc, const float* x, float* out
     a.pmask = h->pmask;
     a.eta = sc->eta;
     a.seed = seed;
-    a.num_layers = g->L;
+    a.num_layers = g->s.L;
     a.noise = noise;
     std::pair<hipEvent_t, hipEvent_t> ev;
     const bool prof = h->profiling && !cap;
@@ -1226,7 +1073,7 @@ static int gen_fused_eps(dpk_handle* h, const float* x, const float* t, float* e
     a.K = 1;
     a.mask = h->mask;
     a.pmask = h->pmask;
-    a.num_layers = g->L;
+    a.num_layers = g->s.L;
     std::pair<hipEvent_t, hipEvent_t> ev;
     const bool prof = h->profiling && !cap;
     if (prof && prof_begin(h, st, ev)) return fail(h, DPK_E_HIP, "dpk_eps: event record");
@@ -1245,8 +1092,8 @@ static int gen_sample(dpk_handle* h, Sched* sc, const float* x, float* out, floa
     if (h->gen->fz) return gen_fused_sample(h, sc, x, out, xs, x0s, N, seed, noise, st, cap);
     GenModel* g = h->gen;
     const int K = sc->K;
-    const long long n = (long long)N * g->J * g->cin;
-    const size_t act = gen_act_floats(g, N), tpf = (size_t)K * g->L * g->D;
+    const long long n = (long long)N * g->s.J * g->s.cin;
+    const size_t act = gen_act_floats(g, N), tpf = (size_t)K * g->s.L * g->s.D;
     float* S = nullptr;
     int rc = gen_scratch_any(h, g, st, cap, act + 2 * (size_t)n + tpf, &S, "dpk_sample");
     if (rc) return rc;
@@ -1256,7 +1103,7 @@ static int gen_sample(dpk_handle* h, Sched* sc, const float* x, float* out, floa
     auto body = [&](hipStream_t s_, float* cur) {
         gen_temb(g, s_, sc->coef + 5, 6, K, tproj);
         for (int s = 0; s < K; ++s) {
-            gen_forward(g, s_, cur, N, tproj + (size_t)s * g->L * g->D, 0, h->mask, h->pmask, eps, S, h->n_cu);
+            gen_forward(g, s_, cur, N, tproj + (size_t)s * g->s.L * g->s.D, 0, h->mask, h->pmask, eps, S, h->n_cu);
             hipLaunchKernelGGL(dpkg::ddim, dim3(gen_blocks(n)), dim3(256), 0, s_, cur, eps, cur,
                                x0s ? x0s + (size_t)s * n : nullptr, n, sc->coef + s * 6, s, sc->eta,
                                (unsigned long long)seed, noise ? noise + (size_t)s * n : nullptr);
@@ -1330,7 +1177,7 @@ static int gen_eps(dpk_handle* h, const float* x, const float* t, float* eps, in
     if (!cap) cap_sweep(h);
     if (h->gen->fz) return gen_fused_eps(h, x, t, eps, N, st, cap);
     GenModel* g = h->gen;
-    const size_t act = gen_act_floats(g, N), tpf = (size_t)N * g->L * g->D;
+    const size_t act = gen_act_floats(g, N), tpf = (size_t)N * g->s.L * g->s.D;
     float* S = nullptr;
     int rc = gen_scratch_any(h, g, st, cap, act + tpf, &S, "dpk_eps");
     if (rc) return rc;
@@ -1339,7 +1186,7 @@ static int gen_eps(dpk_handle* h, const float* x, const float* t, float* eps, in
     const bool prof = h->profiling && !cap;
     if (prof && prof_begin(h, st, ev)) return fail(h, DPK_E_HIP, "dpk_eps: event record");
     gen_temb(g, st, t, 1, N, tproj);
-    gen_forward(g, st, x, N, tproj, g->L * g->D, h->mask, h->pmask, eps, S, h->n_cu);
+    gen_forward(g, st, x, N, tproj, g->s.L * g->s.D, h->mask, h->pmask, eps, S, h->n_cu);
     HIPCHK(h, hipGetLastError());
     if (prof && prof_end(h, st, ev)) return fail(h, DPK_E_HIP, "dpk_eps: event record");
     return DPK_OK;
@@ -1350,7 +1197,7 @@ static int gen_pose(dpk_handle* h, const float* x2d, float* xyz, float* uvxyz, i
                     hipStream_t st, bool cap) {
     if (!cap) cap_sweep(h);
     GenModel* g = h->gen;
-    const size_t act = gen_act_floats(g, N), yn = (size_t)N * g->J * g->cout;
+    const size_t act = gen_act_floats(g, N), yn = (size_t)N * g->s.J * g->s.cout;
     float* S = nullptr;
     int rc = gen_scratch_any(h, g, st, cap, act + yn, &S, "dpk_pose");
     if (rc) return rc;
@@ -1359,8 +1206,8 @@ static int gen_pose(dpk_handle* h, const float* x2d, float* xyz, float* uvxyz, i
     const bool prof = h->profiling && !cap;
     if (prof && prof_begin(h, st, ev)) return fail(h, DPK_E_HIP, "dpk_pose: event record");
     gen_forward(g, st, x2d, N, nullptr, 0, h->mask, h->pmask, y, S, h->n_cu);
-    hipLaunchKernelGGL(dpkg::pose_out, dim3(gen_blocks((long long)N * g->J * (g->cin + g->cout))), dim3(256), 0, st,
-                       x2d, y, N, g->J, g->cin, g->cout, xyz, uvxyz, Hn, root_mode);
+    hipLaunchKernelGGL(dpkg::pose_out, dim3(gen_blocks((long long)N * g->s.J * (g->s.cin + g->s.cout))), dim3(256), 0, st,
+                       x2d, y, N, g->s.J, g->s.cin, g->s.cout, xyz, uvxyz, Hn, root_mode);
     HIPCHK(h, hipGetLastError());
     if (prof && prof_end(h, st, ev)) return fail(h, DPK_E_HIP, "dpk_pose: event record");
     return DPK_OK;

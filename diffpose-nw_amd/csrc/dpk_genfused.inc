@@ -1,7 +1,9 @@
-// The persistent sampler's host side for one compiled model width (round 5): included inside an instance
-// namespace of dpk_sampler.inc (dpkw / dpkw4: hid 128 with 8 / 4 heads, 2-pose tiles; dpkn / dpkn4: hid 64
-// with 2 / 4 heads, 4-pose tiles) by dpk_generic.inc, so every unqualified shape constant below is that
-// instance's.  The generic path (GenFused) calls these for a handle whose shape the instance was compiled for.
+// The persistent sampler's host side for one instance: included by dpk_kernels.hip inside every instance
+// namespace right after dpk_sampler.inc (dpk / dpk2: the shipped shape's 4- and 2-pose tiles; dpkw / dpkw4:
+// hid 128 with 8 / 4 heads, 2-pose tiles; dpkn / dpkn4: hid 64 with 2 / 4 heads, 4-pose tiles), so every
+// unqualified shape constant below is that instance's.  The shipped path (launch_tiles) and the generic
+// path (GenFused, for a handle whose shape an instance was compiled for) call these.
+#include "dpk_pack.inc"
 
 static bool fused_fits(int Dm, int Hm, int Jm, int Lm, int cin, int cout, int kind) {
     return Dm == D && Hm == NH && Jm == J && Lm <= NL && kind == 0 && cin == CIN && cout == COUT;
@@ -12,118 +14,41 @@ static void fused_temb(const float* temb, const float* t, int stride, int count,
     hipLaunchKernelGGL(temb_kernel, dim3((unsigned)count), dim3(256), 0, st, temb, t, stride, out);
 }
 
-// The instance's packed arena and timestep-MLP arena from the generic staging arena (row-major W_eff[k][n],
-// the layouts gen_load writes), the same packing dpk_load_weights / dpk_set_graph do for the shipped shape
-static void fused_pack(GenModel* g) {
-    GenFused* f = g->fz;
-    const float* S = g->h.data();
-    f->ha.assign(ARENA_FLOATS, 0.f);
-    f->ht.assign(TEMB_FLOATS, 0.f);
-    float* A = f->ha.data();
-    for (int l = 0; l < g->L; ++l) {
-        const GenLayer& o = g->lay[l];
-        float* Lw = A + (size_t)l * LAYER_FLOATS;
-        auto at = [&](size_t base, int ld) { return [=](int k, int n) { return S[base + (size_t)k * ld + n]; }; };
-        // QKV with LN0's affine folded in (W' = diag(a) W, c = b W + b_qkv summed in double)
-        pack_blocks(Lw + OFF_QKV, D, D3, KB_D, 3 * NCD,
-                    [&](int k, int n) { return S[o.n0a + k] * S[o.wqkv + (size_t)k * 3 * D + n]; });
-        for (int n = 0; n < D3; ++n) {
-            double cs = 0.0;
-            for (int k = 0; k < D; ++k) cs += (double)S[o.n0b + k] * (double)S[o.wqkv + (size_t)k * 3 * D + n];
-            Lw[OFF_CQKV + n] = (float)(cs + (double)S[o.bqkv + n]);
-            Lw[OFF_BQKV + n] = S[o.bqkv + n];
+// One sample_kernel launch of `blocks` workgroups for the graph pattern (sparse: the compiled H36M one),
+// the noise source (the caller's draws, ZM = 1, or counter-based) and the GEMM mode gm (0 fp32 from W;
+// 1 f16x3 / 2 bf16 from W16, which only the instances with HALF_MODES have kernels for).
+template <int MODE, bool SP, int ZM>
+static void launch_gemm_mode(int gm, dim3 grid, size_t shmem, hipStream_t st, const SampleArgs& a, const float* W,
+                             const char* W16) {
+    if constexpr (HALF_MODES) {
+        if (gm == 1) {
+            hipLaunchKernelGGL((sample_kernel<MODE, SP, 1, ZM>), grid, dim3(NT), shmem, st, a, W, W16);
+            return;
         }
-        pack_blocks(Lw + OFF_O, D, D, KB_D, NCD, at(o.wo, D));
-        pack_blocks(Lw + OFF_FC1, D, D2, KB_D, 2 * NCD, at(o.w1, 2 * D));
-        pack_blocks(Lw + OFF_FC2, D2, D, KB_D2, NCD, at(o.w2, D));
-        pack_blocks(Lw + OFF_C1, D3, D, KB_D3, NCD, at(o.wc1, D));   // [x | T1x | T2x] rows
-        pack_blocks(Lw + OFF_C2, D3, D, KB_D3, NCD, at(o.wc2, D));
-        for (int c = 0; c < D; ++c) {
-            Lw[OFF_BO + c] = S[o.bo + c];
-            Lw[OFF_BFC2 + c] = S[o.b2 + c];
-            Lw[OFF_BC1 + c] = S[o.bc1 + c];
-            Lw[OFF_BC2 + c] = S[o.bc2 + c];
-            Lw[OFF_LN0A + c] = S[o.n0a + c];
-            Lw[OFF_LN0B + c] = S[o.n0b + c];
-            Lw[OFF_LN1A + c] = S[o.n1a + c];
-            Lw[OFF_LN1B + c] = S[o.n1b + c];
-        }
-        for (int c = 0; c < D2; ++c) Lw[OFF_BFC1 + c] = S[o.b1 + c];
-        for (int i = 0; i < J * J; ++i) Lw[OFF_LG + i] = S[o.lg + i];
-        for (int s = 0; s < 5; ++s)
-            for (int ln = 0; ln < 64; ++ln) {
-                const int i = 4 * s + (ln >> 4);
-                Lw[OFF_LGF + s * 64 + ln] = i < J ? S[o.lg + (ln & 15) * J + i] : 0.f;
-                Lw[OFF_LGF + (5 + s) * 64 + ln] = i < J ? S[o.lg + 16 * J + i] : 0.f;
-            }
-    }
-    // input ChebConv: rows k = order * 5 + channel ([3 cin][D] staging rows, the same order); output
-    // ChebConv as Y = x [W0 | W1 | W2] (D -> 3 cout columns)
-    pack_blocks(A + OFF_WIN, 3 * CIN, D, 1, NCD, [&](int k, int n) { return S[g->win + (size_t)k * D + n]; });
-    pack_blocks(A + OFF_WOUT, D, 3 * COUT, KB_D, 1,
-                [&](int k, int n) { return S[g->wout + ((size_t)(n / COUT) * D + k) * COUT + n % COUT]; });
-    for (int c = 0; c < D; ++c) A[OFF_BIN + c] = S[g->bin + c];
-    for (int c = 0; c < 16; ++c) A[OFF_BOUT + c] = c < COUT ? S[g->bout + c] : 0.f;
-    // Chebyshev terms (gen_set_graph's T1 = L, T2 = 2 L L - I): dense, and the H36M-sparse forms when
-    // every nonzero lies inside the compiled pattern
-    const float* T1 = S + g->t1;
-    const float* T2 = S + g->t2;
-    for (int i = 0; i < J * J; ++i) {
-        A[OFF_CHEB + i] = T1[i];
-        A[OFF_CHEB + J * J + i] = T2[i];
-    }
-    bool fits = true;
-    for (int i = 0; i < J; ++i)
-        for (int j = 0; j < J; ++j) {
-            bool in1 = false, in2 = false;
-            for (int k = 0; k < SPAT.n1[i]; ++k) in1 = in1 || SPAT.c1[i][k] == j;
-            for (int k = 0; k < SPAT.n2[i]; ++k) in2 = in2 || SPAT.c2[i][k] == j;
-            if ((!in1 && T1[i * J + j] != 0.f) || (!in2 && T2[i * J + j] != 0.f)) fits = false;
-        }
-    for (int i = 0; i < J; ++i) {
-        for (int k = 0; k < SPAT.n1[i]; ++k) A[OFF_CHEBS + SPAT.o1[i] + k] = T1[i * J + SPAT.c1[i][k]];
-        for (int k = 0; k < SPAT.n2[i]; ++k)
-            A[OFF_CHEBS + SPAT.nnz1 + SPAT.o2[i] + k] = T2[i * J + SPAT.c2[i][k]];
-        float* row = &A[OFF_CHEBT + (size_t)i * (SPT1 + SPT2) * 2];
-        for (int k = 0; k < SPT1 + SPT2; ++k) {
-            const bool t1 = k < SPT1;
-            const int kk = t1 ? k : k - SPT1;
-            const int n = t1 ? SPAT.n1[i] : SPAT.n2[i];
-            const int col = kk < n ? (t1 ? SPAT.c1[i][kk] : SPAT.c2[i][kk]) : i;
-            row[2 * k] = kk < n ? (t1 ? T1 : T2)[i * J + col] : 0.f;
-            const int32_t off = col * LD2;
-            memcpy(&row[2 * k + 1], &off, 4);
-        }
-    }
-    f->sparse = fits;
-    // timestep MLP, transposed [in][out] (the staging rows are already [in][out])
-    float* T = f->ht.data();
-    for (size_t i = 0; i < (size_t)D * E; ++i) T[TOFF_W0 + i] = S[g->d0w + i];
-    for (size_t i = 0; i < (size_t)E * E; ++i) T[TOFF_W1 + i] = S[g->d1w + i];
-    for (int o2 = 0; o2 < E; ++o2) {
-        T[TOFF_B0 + o2] = S[g->d0b + o2];
-        T[TOFF_B1 + o2] = S[g->d1b + o2];
-    }
-    for (size_t i = 0; i < (size_t)g->L * E * D; ++i) T[TOFF_WP + i] = S[g->wtp + i];
-    for (size_t i = 0; i < (size_t)g->L * D; ++i) T[TOFF_BP + i] = S[g->btp + i];
-}
-
-// One sample_kernel launch of ceil(N / P) tiles (P = 2 at hid 128, 4 at hid 64)
-template <int MODE>
-static void fused_launch(GenModel* g, const SampleArgs& a, hipStream_t st) {
-    const dim3 grid((unsigned)((a.N + P - 1) / P)), block(NT);
-    const bool sp = g->fz->sparse;
-    const float* W = g->fz->arena;
-#define DPK_LAUNCHW(SP, ZZ) hipLaunchKernelGGL((sample_kernel<MODE, SP, 0, ZZ>), grid, block, 0, st, a, W, nullptr)
-    if constexpr (MODE == M_SAMPLE) {
-        if (a.noise) {      // the caller's draws (ZM = 1)
-            if (sp) DPK_LAUNCHW(true, 1);
-            else DPK_LAUNCHW(false, 1);
+        if (gm == 2) {
+            hipLaunchKernelGGL((sample_kernel<MODE, SP, 2, ZM>), grid, dim3(NT), shmem, st, a, W, W16);
             return;
         }
     }
-    if (sp) DPK_LAUNCHW(true, 0);
-    else DPK_LAUNCHW(false, 0);
-#undef DPK_LAUNCHW
+    hipLaunchKernelGGL((sample_kernel<MODE, SP, 0, ZM>), grid, dim3(NT), shmem, st, a, W, W16);
+}
+template <int MODE>
+static void launch_sample(bool sparse, int gm, int blocks, size_t shmem, hipStream_t st, const SampleArgs& a,
+                          const float* W, const char* W16) {
+    const dim3 grid((unsigned)blocks);
+    if constexpr (MODE == M_SAMPLE) {
+        if (a.noise) {
+            if (sparse) launch_gemm_mode<MODE, true, 1>(gm, grid, shmem, st, a, W, W16);
+            else launch_gemm_mode<MODE, false, 1>(gm, grid, shmem, st, a, W, W16);
+            return;
+        }
+    }
+    if (sparse) launch_gemm_mode<MODE, true, 0>(gm, grid, shmem, st, a, W, W16);
+    else launch_gemm_mode<MODE, false, 0>(gm, grid, shmem, st, a, W, W16);
 }
 
+// ceil(N / P) tiles (P = 2 at hid 128, 4 at hid 64), fp32 GEMMs
+template <int MODE>
+static void fused_launch(bool sparse, const float* arena, const SampleArgs& a, hipStream_t st) {
+    launch_sample<MODE>(sparse, 0, (a.N + P - 1) / P, 0, st, a, arena, nullptr);
+}

@@ -109,14 +109,18 @@ struct SampleArgs {
 };
 }  // namespace dpk_shared
 
+#include "dpk_stage.inc"
+
 #define DPK_P 4
 namespace dpk {
 #include "dpk_sampler.inc"
+#include "dpk_genfused.inc"
 }  // namespace dpk
 #undef DPK_P
 #define DPK_P 2
 namespace dpk2 {
 #include "dpk_sampler.inc"
+#include "dpk_genfused.inc"
 }  // namespace dpk2
 // The persistent sampler at a wider model (round 5): hid 128 / 8 heads (d_k 16), 2-pose tiles (4-pose
 // tiles of 128-wide rows do not fit 160 KB of LDS), fp32 GEMMs; run by the generic-shape path for that
@@ -129,6 +133,7 @@ namespace dpk2 {
 #define DPK_NH 8
 namespace dpkw {
 #include "dpk_sampler.inc"
+#include "dpk_genfused.inc"
 }  // namespace dpkw
 #undef DPK_NH
 #undef DPK_D
@@ -139,6 +144,7 @@ namespace dpkw {
 #define DPK_NH 4
 namespace dpkw4 {
 #include "dpk_sampler.inc"
+#include "dpk_genfused.inc"
 }  // namespace dpkw4
 #undef DPK_NH
 #undef DPK_D
@@ -150,11 +156,13 @@ namespace dpkw4 {
 #define DPK_NH 2
 namespace dpkn {
 #include "dpk_sampler.inc"
+#include "dpk_genfused.inc"
 }  // namespace dpkn
 #undef DPK_NH
 #define DPK_NH 4
 namespace dpkn4 {
 #include "dpk_sampler.inc"
+#include "dpk_genfused.inc"
 }  // namespace dpkn4
 #undef DPK_NH
 #undef DPK_D
@@ -277,21 +285,16 @@ struct dpk_handle {
     std::vector<Sched*> retired;   // replaced schedules not yet known to be unused
     std::vector<EpsBuf> eps_bufs;  // per stream (uncaptured dpk_eps)
     EpsBuf eps_spare;              // unused buffer for the next capture's dpk_eps (no stream)
-    std::vector<float> h_arena;    // host staging of the arena
+    Stage stage;                   // host staging of the weights and the graph (the shipped shape; else gen's)
+    Packed pk;                     // the arenas packed from it (dpk::pack_model), as uploaded
     char* arena16 = nullptr;       // device: split-fp16 GEMM weights (gemm mode 1)
-    std::vector<uint16_t> h_arena16;
     char* arenabf = nullptr;       // device: bf16 GEMM weights (gemm mode 2), same layout
-    std::vector<uint16_t> h_arenabf;
     int gemm_mode = 0;             // 0: fp32 MFMA, 1: 3x fp16-split MFMA, 2: bf16 MFMA (dpk_set_gemm_mode)
-    bool w16_ok = true;            // loaded weights fit the split-fp16 packing (|w| < 1015)
-    std::vector<float> h_temb;
     bool have_graph = false, have_weights = false;
     unsigned mask = (1u << J) - 1u;
     const unsigned* pmask = nullptr;   // dpk_set_pose_masks: caller-owned device array
     int pmask_n = 0;
-    std::vector<float> h_adj;
     bool profiling = false;
-    bool sparse_graph = false;     // adjacency matches the compiled H36M Chebyshev pattern
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_used, ev_free;
 #if DPK_TRACE
     unsigned long long* trace = nullptr;
@@ -328,93 +331,6 @@ static int fail(dpk_handle* h, int code, const std::string& msg) {
         if (e_ != hipSuccess)                                                                  \
             return fail((h), DPK_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));    \
     } while (0)
-
-// Pack W_eff (K x N, W_eff(k, n)) into MFMA B-fragment blocks [NC][KB][64][4].
-template <class F>
-static void pack_blocks(float* dst, int Kreal, int Nreal, int KB, int NC, F w) {
-    for (int ct = 0; ct < NC; ++ct)
-        for (int kb = 0; kb < KB; ++kb)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int j = 0; j < 4; ++j) {
-                    const int k = kb * 16 + 4 * (lane >> 4) + j;
-                    const int n = ct * 16 + (lane & 15);
-                    dst[((size_t)(ct * KB + kb) * 64 + lane) * 4 + j] = (k < Kreal && n < Nreal) ? w(k, n) : 0.f;
-                }
-}
-
-// Host fp32 -> bf16, round to nearest even (finite inputs).
-static inline uint16_t bf16_rne(float v) {
-    uint32_t u = __builtin_bit_cast(uint32_t, v);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-static inline float bf16_to_f32(uint16_t b) { return __builtin_bit_cast(float, (uint32_t)b << 16); }
-
-// Split W_eff * W16_SCALE into 16x16x32 B fragments for the half-width-operand GEMMs (gemmh_pass):
-// lane l holds column n = ct*16 + (l&15) at the 8 k of its lane group g = l>>4 in the order
-// 4g..4g+3, 16+4g..16+4g+3 of the 32-block (the A fragments' order: two fp32 16x16x4 fragments).
-// BF = false (gemm mode 1, f16x3): blocks [NC][KB32][hi 1 KiB | lo 1 KiB], hi = fp16(v) (RNE),
-//   lo = fp16(v - hi) (v - hi is exact in fp32, Sterbenz);
-// BF = true (gemm mode 2, bf16): blocks [NC][KB32][1 KiB] of bf16(v) (RNE).
-template <bool BF = false, class F>
-static float pack16(uint16_t* dst, int Kreal, int Nreal, int KB32, int NC, F w) {
-    constexpr size_t blk = BF ? 512 : 1024;      // uint16 per block
-    float wmax = 0.f;
-    for (int ct = 0; ct < NC; ++ct)
-        for (int kb = 0; kb < KB32; ++kb)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int i = 0; i < 8; ++i) {
-                    const int g = lane >> 4;
-                    const int k = kb * 32 + (i < 4 ? 4 * g + i : 16 + 4 * g + (i - 4));
-                    const int n = ct * 16 + (lane & 15);
-                    const float v = (k < Kreal && n < Nreal) ? w(k, n) * W16_SCALE : 0.f;
-                    wmax = fmaxf(wmax, fabsf(v));
-                    const size_t base = (size_t)(ct * KB32 + kb) * blk;
-                    if constexpr (BF) {
-                        dst[base + lane * 8 + i] = bf16_rne(v);
-                    } else {
-                        const _Float16 hi = (_Float16)v;
-                        const _Float16 lo = (_Float16)(v - (float)hi);
-                        dst[base + lane * 8 + i] = __builtin_bit_cast(uint16_t, hi);
-                        dst[base + 512 + lane * 8 + i] = __builtin_bit_cast(uint16_t, lo);
-                    }
-                }
-    return wmax;
-}
-
-
-// Chebyshev terms of the normalised Laplacian, fp32 in the reference's operation order
-// (ChebConv.py:114-130, :90-112): d = rowsum^-1/2; L = I - (d_i g_ij) d_j; T2 = 2 L@L - I.
-static void cheb_terms(const float* g, float* T1, float* T2) {
-    float d[J];
-    for (int i = 0; i < J; ++i) {
-        float s = 0.f;
-        for (int j = 0; j < J; ++j) s += g[i * J + j];
-        d[i] = 1.0f / sqrtf(s);
-    }
-    float L[J * J];
-    for (int i = 0; i < J; ++i)
-        for (int j = 0; j < J; ++j) L[i * J + j] = (i == j ? 1.f : 0.f) - (d[i] * g[i * J + j]) * d[j];
-    for (int i = 0; i < J; ++i)
-        for (int j = 0; j < J; ++j) {
-            float acc = 0.f;
-            for (int k = 0; k < J; ++k) acc += L[i * J + k] * L[k * J + j];
-            T1[i * J + j] = L[i * J + j];
-            T2[i * J + j] = 2.f * acc - (i == j ? 1.f : 0.f);
-        }
-}
-
-// GraphNet Laplacian (GraFormer.py:174-178): c_k = colsum_k + 1e-5; L = c_i^-1/2 A_ij c_j^-1/2.
-static void graph_lap(const float* A, float* Lg) {
-    float dh[J];
-    for (int k = 0; k < J; ++k) {
-        float s = 0.f;
-        for (int i = 0; i < J; ++i) s += A[i * J + k];
-        dh[k] = 1.0f / sqrtf(s + 1e-5f);
-    }
-    for (int i = 0; i < J; ++i)
-        for (int j = 0; j < J; ++j) Lg[i * J + j] = (dh[i] * A[i * J + j]) * dh[j];
-}
 
 // Is `st` capturing a graph right now?  (Launches then become graph nodes: nothing may be
 // allocated or freed, and the schedule they read must outlive the graph.)
@@ -569,12 +485,12 @@ static int upload(dpk_handle* h) {
     sched_sweep(h);
     if (!h->arena) HIPCHK(h, hipMalloc(&h->arena, (size_t)ARENA_FLOATS * 4));
     if (!h->arena16) HIPCHK(h, hipMalloc(&h->arena16, (size_t)ARENA16_BYTES));
-    HIPCHK(h, hipMemcpy(h->arena16, h->h_arena16.data(), (size_t)ARENA16_BYTES, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->arena16, h->pk.a16.data(), (size_t)ARENA16_BYTES, hipMemcpyHostToDevice));
     if (!h->arenabf) HIPCHK(h, hipMalloc(&h->arenabf, (size_t)ARENAB_BYTES));
-    HIPCHK(h, hipMemcpy(h->arenabf, h->h_arenabf.data(), (size_t)ARENAB_BYTES, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->arenabf, h->pk.abf.data(), (size_t)ARENAB_BYTES, hipMemcpyHostToDevice));
     if (!h->temb) HIPCHK(h, hipMalloc(&h->temb, (size_t)TEMB_FLOATS * 4));
-    HIPCHK(h, hipMemcpy(h->arena, h->h_arena.data(), (size_t)ARENA_FLOATS * 4, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(h->temb, h->h_temb.data(), (size_t)TEMB_FLOATS * 4, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->arena, h->pk.arena.data(), (size_t)ARENA_FLOATS * 4, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->temb, h->pk.temb.data(), (size_t)TEMB_FLOATS * 4, hipMemcpyHostToDevice));
     ++h->weights_gen;
     if (!h->have_weights || h->kind != 0) return DPK_OK;
     // every live schedule (current, retired, pinned by a graph) follows the new weights
@@ -644,31 +560,9 @@ static int split_slot_hold(dpk_handle* h, int slot, hipStream_t st) {
 // pattern and GEMM mode.
 template <int MODE, int PT>
 static void launch_tiles(dpk_handle* h, int blocks, size_t shmem, hipStream_t st, const SampleArgs& a) {
-    const int gm = h->gemm_mode;
-    const char* a16 = gm == 2 ? h->arenabf : h->arena16;
-    const dim3 grid(blocks), block(NT);
-#define DPK_LAUNCH3(NS, SP, NZ)                                                                                   \
-    do {                                                                                                        \
-        if (gm == 1) hipLaunchKernelGGL((NS::sample_kernel<MODE, SP, 1, NZ>), grid, block, shmem, st, a, h->arena, a16); \
-        else if (gm == 2) hipLaunchKernelGGL((NS::sample_kernel<MODE, SP, 2, NZ>), grid, block, shmem, st, a, h->arena, a16); \
-        else hipLaunchKernelGGL((NS::sample_kernel<MODE, SP, 0, NZ>), grid, block, shmem, st, a, h->arena, a16);  \
-    } while (0)
-#define DPK_LAUNCH(NS)                                                                                          \
-    do {                                                                                                        \
-        if constexpr (MODE == M_SAMPLE) {                                                                       \
-            if (a.noise) {      /* the caller's draws (ZM = 1) */                                               \
-                if (h->sparse_graph) DPK_LAUNCH3(NS, true, 1);                                                  \
-                else DPK_LAUNCH3(NS, false, 1);                                                                 \
-                break;                                                                                          \
-            }                                                                                                   \
-        }                                                                                                       \
-        if (h->sparse_graph) DPK_LAUNCH3(NS, true, 0);                                                          \
-        else DPK_LAUNCH3(NS, false, 0);                                                                         \
-    } while (0)
-    if constexpr (PT == 4) DPK_LAUNCH(dpk);
-    else DPK_LAUNCH(dpk2);
-#undef DPK_LAUNCH
-#undef DPK_LAUNCH3
+    const char* a16 = h->gemm_mode == 2 ? h->arenabf : h->arena16;
+    if constexpr (PT == 4) dpk::launch_sample<MODE>(h->pk.sparse, h->gemm_mode, blocks, shmem, st, a, h->arena, a16);
+    else dpk2::launch_sample<MODE>(h->pk.sparse, h->gemm_mode, blocks, shmem, st, a, h->arena, a16);
 }
 
 // The sampler over a.N poses.  One 4-pose workgroup per CU per round; a partial last round of r
@@ -768,7 +662,8 @@ int dpk_create(const dpk_config* cfg, dpk_handle** out) {
     h->num_layers = cfg->num_layers;
     h->n_pts = cfg->n_pts;
     h->mask = cfg->n_pts >= 32 ? ~0u : (1u << cfg->n_pts) - 1u;   // every key attends (all-ones src_mask)
-    if (!compiled)
+    if (compiled) stage_init(h->stage, D, NH, J, cfg->num_layers, cfg->coords_in, cfg->coords_out, kind);
+    else
         h->gen = gen_new(cfg->hid_dim, cfg->n_head, cfg->n_pts, cfg->num_layers, cfg->coords_in, cfg->coords_out, kind);
     if (hipSetDevice(h->device) != hipSuccess ||
         hipStreamCreateWithFlags(&h->aux, hipStreamNonBlocking) != hipSuccess ||
@@ -792,10 +687,6 @@ int dpk_create(const dpk_config* cfg, dpk_handle** out) {
         delete h;
         return DPK_E_HIP;
     }
-    h->h_arena.assign(ARENA_FLOATS, 0.f);
-    h->h_arena16.assign(ARENA16_BYTES / 2, 0);
-    h->h_arenabf.assign(ARENAB_BYTES / 2, 0);
-    h->h_temb.assign(TEMB_FLOATS, 0.f);
     *out = h;
     return DPK_OK;
 }
@@ -835,51 +726,19 @@ void dpk_destroy(dpk_handle* h) {
 
 const char* dpk_last_error(const dpk_handle* h) { return h ? h->err.c_str() : "null handle"; }
 
+// Repack the handle's arenas from its staging and upload them (weights loaded; the graph's terms are zeros
+// until dpk_set_graph).  Weights and graphs are loaded rarely, so everything is repacked every time.
+static int pack_upload(dpk_handle* h) {
+    if (h->gen) return gen_upload(h, h->gen);
+    dpk::pack_model(h->stage, h->pk, true);
+    return upload(h);
+}
+
 int dpk_set_graph(dpk_handle* h, const float* adj) {
     if (!h || !adj) return fail(h, DPK_E_INVALID, "dpk_set_graph: null argument");
-    if (h->gen) {
-        gen_set_graph(h->gen, adj);
-        h->have_graph = true;
-        return h->have_weights ? gen_upload(h, h->gen) : DPK_OK;
-    }
-    float T1[J * J], T2[J * J];
-    cheb_terms(adj, T1, T2);
-    for (int i = 0; i < J * J; ++i) {
-        h->h_arena[OFF_CHEB + i] = T1[i];
-        h->h_arena[OFF_CHEB + J * J + i] = T2[i];
-    }
-    // sparse path iff every nonzero of T1/T2 lies inside the compiled H36M pattern
-    bool fits = true;
-    for (int i = 0; i < J; ++i)
-        for (int j = 0; j < J; ++j) {
-            bool in1 = false, in2 = false;
-            for (int k = 0; k < SPAT.n1[i]; ++k) in1 = in1 || SPAT.c1[i][k] == j;
-            for (int k = 0; k < SPAT.n2[i]; ++k) in2 = in2 || SPAT.c2[i][k] == j;
-            if ((!in1 && T1[i * J + j] != 0.f) || (!in2 && T2[i * J + j] != 0.f)) fits = false;
-        }
-    for (int i = 0; i < J; ++i) {
-        for (int k = 0; k < SPAT.n1[i]; ++k) h->h_arena[OFF_CHEBS + SPAT.o1[i] + k] = T1[i * J + SPAT.c1[i][k]];
-        for (int k = 0; k < SPAT.n2[i]; ++k)
-            h->h_arena[OFF_CHEBS + SPAT.nnz1 + SPAT.o2[i] + k] = T2[i * J + SPAT.c2[i][k]];
-    }
-    // padded rows of the same values for the output ChebConv (OFF_CHEBT): (value bits, row offset j'*LD2)
-    for (int i = 0; i < J; ++i) {
-        float* row = &h->h_arena[OFF_CHEBT + (size_t)i * (SPT1 + SPT2) * 2];
-        for (int k = 0; k < SPT1 + SPT2; ++k) {
-            const bool t1 = k < SPT1;
-            const int kk = t1 ? k : k - SPT1;
-            const int n = t1 ? SPAT.n1[i] : SPAT.n2[i];
-            const int col = kk < n ? (t1 ? SPAT.c1[i][kk] : SPAT.c2[i][kk]) : i;
-            row[2 * k] = kk < n ? (t1 ? T1 : T2)[i * J + col] : 0.f;
-            const int32_t off = col * LD2;
-            memcpy(&row[2 * k + 1], &off, 4);
-        }
-    }
-    h->sparse_graph = fits;
-    h->h_adj.assign(adj, adj + J * J);
+    stage_set_graph(h->gen ? h->gen->s : h->stage, adj);
     h->have_graph = true;
-    if (h->have_weights) return upload(h);
-    return DPK_OK;
+    return h->have_weights ? pack_upload(h) : DPK_OK;
 }
 
 int dpk_set_mask(dpk_handle* h, const uint8_t* m) {
@@ -910,178 +769,14 @@ static int check_pose_masks(dpk_handle* h, int N, const char* who) {
 int dpk_load_weights(dpk_handle* h, const char* const* names, const float* const* ptrs, const int64_t* numels,
                      int n) {
     if (!h || !names || !ptrs || !numels || n <= 0) return fail(h, DPK_E_INVALID, "dpk_load_weights: bad args");
-    std::unordered_map<std::string, std::pair<const float*, int64_t>> sd;
-    for (int i = 0; i < n; ++i) {
+    for (int i = 0; i < n; ++i)
         if (!names[i] || !ptrs[i]) return fail(h, DPK_E_INVALID, "dpk_load_weights: null entry");
-        std::string k = names[i];
-        if (k.rfind("module.", 0) == 0) k = k.substr(7);
-        sd[k] = {ptrs[i], numels[i]};
-    }
-    std::string missing;
-    auto get = [&](const std::string& k, int64_t numel) -> const float* {
-        auto it = sd.find(k);
-        if (it == sd.end()) {
-            missing = "missing key " + k;
-            return nullptr;
-        }
-        if (it->second.second != numel) {
-            missing = "size mismatch for " + k;
-            return nullptr;
-        }
-        return it->second.first;
-    };
-    if (h->gen) {
-        if (!gen_load(h->gen, get)) return fail(h, DPK_E_WEIGHTS, "dpk_load_weights: " + missing);
-        h->have_weights = true;
-        return gen_upload(h, h->gen);
-    }
-#define GET(var, key, numel)                                             \
-    const float* var = get(key, numel);                                  \
-    if (!var) return fail(h, DPK_E_WEIGHTS, "dpk_load_weights: " + missing);
-
-    const bool pose = h->kind == 1;
-    const int cin = pose ? CIN_POSE : CIN, cout = pose ? COUT_POSE : COUT;
-    float* A = h->h_arena.data();
-    float w16max = 0.f;             // largest |64 w| of the split-fp16 GEMM weights
-    for (int l = 0; l < h->num_layers; ++l) {
-        float* Lw = A + (size_t)l * LAYER_FLOATS;
-        const std::string at = "atten_layers." + std::to_string(l) + ".";
-        const std::string gc = "gconv_layers." + std::to_string(l) + ".";
-        GET(wq, at + "self_attn.linears.0.weight", D * D);
-        GET(wk, at + "self_attn.linears.1.weight", D * D);
-        GET(wv, at + "self_attn.linears.2.weight", D * D);
-        GET(wo, at + "self_attn.linears.3.weight", D * D);
-        GET(bq, at + "self_attn.linears.0.bias", D);
-        GET(bk, at + "self_attn.linears.1.bias", D);
-        GET(bv, at + "self_attn.linears.2.bias", D);
-        GET(bo, at + "self_attn.linears.3.bias", D);
-        GET(ahat, at + "feed_forward.A_hat", J * J);
-        GET(f1w, at + "feed_forward.gconv1.fc.weight", D2 * D);
-        GET(f1b, at + "feed_forward.gconv1.fc.bias", D2);
-        GET(f2w, at + "feed_forward.gconv2.fc.weight", D * D2);
-        GET(f2b, at + "feed_forward.gconv2.fc.bias", D);
-        GET(n0a, at + "sublayer.0.norm.a_2", D);
-        GET(n0b, at + "sublayer.0.norm.b_2", D);
-        GET(n1a, at + "sublayer.1.norm.a_2", D);
-        GET(n1b, at + "sublayer.1.norm.b_2", D);
-        GET(c1w, gc + "gconv1.gconv.weight", 3 * D * D);
-        GET(c1b, gc + "gconv1.gconv.bias", D);
-        GET(c2w, gc + "gconv2.gconv.weight", 3 * D * D);
-        GET(c2b, gc + "gconv2.gconv.bias", D);
-        const float* tpw = nullptr;
-        const float* tpb = nullptr;
-        if (!pose) {     // GCNpose's _ResChebGC has no temb_proj (models/ChebConv.py:154-165)
-            GET(tpw_, gc + "temb_proj.weight", D * E);
-            GET(tpb_, gc + "temb_proj.bias", D);
-            tpw = tpw_;
-            tpb = tpb_;
-        }
-        // nn.Linear weight is (out, in): W_eff[k][n] = weight[n][k]
-        auto wqkv = [&](int k, int n) {
-            const float* w = n < D ? wq : (n < 2 * D ? wk : wv);
-            return w[(n % D) * D + k];
-        };
-        // QKV GEMM with LN0's affine folded in (the LN phase writes (x - mean) / (std + eps)):
-        // W' = diag(a) W, bias c = b W + b_qkv (summed in double)
-        pack_blocks(Lw + OFF_QKV, D, D3, KB_D, 18, [&](int k, int n) { return n0a[k] * wqkv(k, n); });
-        for (int n = 0; n < D3; ++n) {
-            double cs = 0.0;
-            for (int k = 0; k < D; ++k) cs += (double)n0b[k] * (double)wqkv(k, n);
-            const float bqkv = n < D ? bq[n] : (n < 2 * D ? bk[n - D] : bv[n - 2 * D]);
-            Lw[OFF_CQKV + n] = (float)(cs + (double)bqkv);
-        }
-        pack_blocks(Lw + OFF_O, D, D, KB_D, 6, [&](int k, int n) { return wo[n * D + k]; });
-        pack_blocks(Lw + OFF_FC1, D, D2, KB_D, 12, [&](int k, int n) { return f1w[n * D + k]; });
-        pack_blocks(Lw + OFF_FC2, D2, D, KB_D2, 6, [&](int k, int n) { return f2w[n * D2 + k]; });
-        // ChebConv weight (3,1,in,out): the GEMMs read [x | T1x | T2x] (x from its own buffer,
-        // cheb_prep XSKIP), the reference's row order
-        pack_blocks(Lw + OFF_C1, D3, D, KB_D3, 6, [&](int k, int n) { return c1w[k * D + n]; });
-        pack_blocks(Lw + OFF_C2, D3, D, KB_D3, 6, [&](int k, int n) { return c2w[k * D + n]; });
-        // the half-width-operand GEMMs (modes 1, 2) read the fp32 mode's operands: LN0 folded into QKV
-        // (bias OFF_CQKV), the Chebyshev GEMMs' [x | T1x | T2x] in the reference's row order
-        auto wqkv_f = [&](int k, int n) { return n0a[k] * wqkv(k, n); };
-        auto wo_f = [&](int k, int n) { return wo[n * D + k]; };
-        auto f1_f = [&](int k, int n) { return f1w[n * D + k]; };
-        auto f2_f = [&](int k, int n) { return f2w[n * D2 + k]; };
-        auto c1_f = [&](int k, int n) { return c1w[k * D + n]; };
-        auto c2_f = [&](int k, int n) { return c2w[k * D + n]; };
-        uint16_t* L16 = h->h_arena16.data() + (size_t)l * LAYER16_BYTES / 2;
-        w16max = fmaxf(w16max, pack16(L16 + O16_QKV / 2, D, D3, KB32_D, 18, wqkv_f));
-        w16max = fmaxf(w16max, pack16(L16 + O16_O / 2, D, D, KB32_D, 6, wo_f));
-        w16max = fmaxf(w16max, pack16(L16 + O16_FC1 / 2, D, D2, KB32_D, 12, f1_f));
-        w16max = fmaxf(w16max, pack16(L16 + O16_FC2 / 2, D2, D, KB32_D2, 6, f2_f));
-        w16max = fmaxf(w16max, pack16(L16 + O16_C1 / 2, D3, D, KB32_D3, 6, c1_f));
-        w16max = fmaxf(w16max, pack16(L16 + O16_C2 / 2, D3, D, KB32_D3, 6, c2_f));
-        uint16_t* Lb = h->h_arenabf.data() + (size_t)l * LAYER16_BYTES / 4;     // bf16 blocks: half the bytes
-        (void)pack16<true>(Lb + O16_QKV / 4, D, D3, KB32_D, 18, wqkv_f);
-        (void)pack16<true>(Lb + O16_O / 4, D, D, KB32_D, 6, wo_f);
-        (void)pack16<true>(Lb + O16_FC1 / 4, D, D2, KB32_D, 12, f1_f);
-        (void)pack16<true>(Lb + O16_FC2 / 4, D2, D, KB32_D2, 6, f2_f);
-        (void)pack16<true>(Lb + O16_C1 / 4, D3, D, KB32_D3, 6, c1_f);
-        (void)pack16<true>(Lb + O16_C2 / 4, D3, D, KB32_D3, 6, c2_f);
-        for (int c = 0; c < D; ++c) {
-            Lw[OFF_BQKV + c] = bq[c];
-            Lw[OFF_BQKV + D + c] = bk[c];
-            Lw[OFF_BQKV + 2 * D + c] = bv[c];
-            Lw[OFF_BO + c] = bo[c];
-            Lw[OFF_BFC2 + c] = f2b[c];
-            Lw[OFF_BC1 + c] = c1b[c];
-            Lw[OFF_BC2 + c] = c2b[c];
-            Lw[OFF_LN0A + c] = n0a[c];
-            Lw[OFF_LN0B + c] = n0b[c];
-            Lw[OFF_LN1A + c] = n1a[c];
-            Lw[OFF_LN1B + c] = n1b[c];
-        }
-        for (int c = 0; c < D2; ++c) Lw[OFF_BFC1 + c] = f1b[c];
-        graph_lap(ahat, Lw + OFF_LG);
-        for (int s = 0; s < 5; ++s)
-            for (int ln = 0; ln < 64; ++ln) {
-                const int i = 4 * s + (ln >> 4);
-                Lw[OFF_LGF + s * 64 + ln] = i < J ? Lw[OFF_LG + (ln & 15) * J + i] : 0.f;
-                Lw[OFF_LGF + (5 + s) * 64 + ln] = i < J ? Lw[OFF_LG + 16 * J + i] : 0.f;
-            }
-        // temb_proj: transposed [in=384][out=96]
-        if (!pose) {
-            float* T = h->h_temb.data();
-            for (int o = 0; o < D; ++o) {
-                for (int k = 0; k < E; ++k) T[TOFF_WP + (size_t)l * E * D + k * D + o] = tpw[o * E + k];
-                T[TOFF_BP + l * D + o] = tpb[o];
-            }
-        }
-    }
-    // fp16 hi parts must stay finite: |64 w| below the largest fp16 (65504), with margin
-    h->w16_ok = w16max < 65000.f;
-    GET(wi, "gconv_input.weight", 3 * cin * D);
-    GET(bi, "gconv_input.bias", D);
-    GET(wout, "gconv_output.weight", 3 * D * cout);
-    GET(bout, "gconv_output.bias", cout);
-    // input rows k = order*5 + channel of the 5-channel tile; GCNpose's channels 2-4 are zero
-    pack_blocks(A + OFF_WIN, 3 * CIN, D, 1, 6, [&](int k, int n) {
-        const int o = k / CIN, c = k % CIN;
-        return c < cin ? wi[o * cin * D + c * D + n] : 0.f;
-    });
-    // output ChebConv as Y = x [W0 | W1 | W2] (96 -> 3*cout columns), out = Y0 + T1 Y1 + T2 Y2 in the kernel
-    pack_blocks(A + OFF_WOUT, D, 3 * cout, KB_D, 1,
-                [&](int k, int n) { return wout[((n / cout) * D + k) * cout + n % cout]; });
-    for (int c = 0; c < D; ++c) A[OFF_BIN + c] = bi[c];
-    for (int c = 0; c < 16; ++c) A[OFF_BOUT + c] = c < cout ? bout[c] : 0.f;
-    if (!pose) {         // GCNpose carries temb.dense too (gcnpose.py:94-98) but never uses it
-        GET(d0w, "temb.dense.0.weight", E * D);
-        GET(d0b, "temb.dense.0.bias", E);
-        GET(d1w, "temb.dense.1.weight", E * E);
-        GET(d1b, "temb.dense.1.bias", E);
-        float* T = h->h_temb.data();
-        for (int o = 0; o < E; ++o) {
-            for (int k = 0; k < D; ++k) T[TOFF_W0 + k * E + o] = d0w[o * D + k];
-            for (int k = 0; k < E; ++k) T[TOFF_W1 + k * E + o] = d1w[o * E + k];
-            T[TOFF_B0 + o] = d0b[o];
-            T[TOFF_B1 + o] = d1b[o];
-        }
-    }
-#undef GET
+    std::string err;
+    if (!stage_load(h->gen ? h->gen->s : h->stage, names, ptrs, numels, n, err))
+        return fail(h, DPK_E_WEIGHTS, "dpk_load_weights: " + err);
     h->have_weights = true;
-    int rc = upload(h);
-    if (rc || !pose) return rc;
+    const int rc = pack_upload(h);
+    if (rc || h->gen || h->kind == 0) return rc;
     // the pose backbone adds no timestep projection: a zero row per layer (E_CHEB1 adds +0)
     if (!h->tproj_zero) {
         HIPCHK(h, hipMalloc(&h->tproj_zero, (size_t)NL * D * 4));
@@ -1169,7 +864,7 @@ static int check_ready(dpk_handle* h, int kind = 0) {
     if (h->gen && h->gemm_mode != 0)
         return fail(h, DPK_E_UNSUPPORTED, "generic-shape path (model shape other than hid 96 / 4 heads / 17 joints): "
                                           "fp32 GEMMs only (gemm mode 0)");
-    if (h->gemm_mode == 1 && !h->w16_ok)
+    if (h->gemm_mode == 1 && !h->pk.w16_ok)
         return fail(h, DPK_E_UNSUPPORTED, "gemm mode 1 (3x fp16): a GEMM weight has |w| >= 1015, outside the split-fp16 "
                                           "packing range; use gemm mode 0 (fp32)");
     return DPK_OK;

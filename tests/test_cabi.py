@@ -89,3 +89,42 @@ def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     monkeypatch.setattr(_lib, "_LIB", None)
     with pytest.raises(ImportError):
         _lib.lib()
+
+
+@pytest.mark.gpu
+def test_failed_load_keeps_the_loaded_weights():
+    """dpk_load_weights is all or nothing: a state_dict of other values with its last-read key removed
+    returns DPK_E_WEIGHTS (the message names the key) and leaves the handle's staged weights alone, so the
+    repack and upload of a later dpk_set_graph (same adjacency) samples bitwise what it sampled before."""
+    import numpy as np
+    import torch
+
+    from diffpose_amd.data import synthetic_batch
+    from diffpose_amd.gcndiff import HipGCNdiff, _f32p, adj_mx_from_edges
+    from diffpose_amd.schedule import get_beta_schedule, make_seq
+    from diffpose_amd.weights import synthetic_state_dict
+
+    if not torch.cuda.is_available():
+        pytest.skip("no HIP device")
+    L = _lib.lib()
+    adj = adj_mx_from_edges()
+    m = HipGCNdiff(adj, None, device="cuda:0")
+    m.load_state_dict(synthetic_state_dict())
+    x = torch.from_numpy(synthetic_batch(8, seed=5)[0]).cuda()
+    seq = make_seq("uniform", 50, 2)
+    b = torch.from_numpy(get_beta_schedule("linear", beta_start=1e-4, beta_end=1e-3, num_diffusion_timesteps=51)).float()
+    first = m.sample(x, seq, b).cpu().numpy()
+
+    other = synthetic_state_dict(seed=77)
+    del other["temb.dense.1.bias"]
+    names = list(other)
+    arrs = [np.ascontiguousarray(other[k], dtype=np.float32) for k in names]
+    c_names = (ctypes.c_char_p * len(names))(*[k.encode() for k in names])
+    c_ptrs = (ctypes.POINTER(ctypes.c_float) * len(arrs))(*[_f32p(a) for a in arrs])
+    c_num = (ctypes.c_int64 * len(arrs))(*[a.size for a in arrs])
+    assert L.dpk_load_weights(m._h, c_names, c_ptrs, c_num, len(arrs)) == -5      # DPK_E_WEIGHTS
+    assert L.dpk_last_error(m._h) == b"dpk_load_weights: missing key temb.dense.1.bias"
+    _lib.check(m._h, "dpk_set_graph", L.dpk_set_graph(m._h, _f32p(np.ascontiguousarray(adj, dtype=np.float32))))
+    again = m.sample(x, seq, b).cpu().numpy()
+    m.close()
+    assert np.array_equal(first, again), float(np.abs(first.astype(np.float64) - again).max())
