@@ -611,11 +611,6 @@ __global__ void __launch_bounds__(256) pose_out(const float* __restrict__ x2d, c
 
 // ---------------------------------------------------------------------------------------
 // Host side of the generic path
-struct GenScratch {
-    hipStream_t st = nullptr;
-    float* p = nullptr;
-    size_t cap = 0;   // floats
-};
 // The generic path's K-step loop recorded as one hipGraph (north_star: the K-step loop as a hipGraph;
 // on this path a step is 13 launches per layer plus 6): recorded on the handle's own stream, replayed
 // with one hipGraphLaunch on the caller's stream.  It reads only handle-owned memory (the caller
@@ -665,8 +660,6 @@ struct GenModel {
     std::vector<float> hp;     // host staging of the packed arena
     float* devp = nullptr;     // device packed arena
     float* dev = nullptr;      // device arena
-    std::vector<GenScratch> scratch;
-    GenScratch spare;          // for the next capture (CapRes::gen): sized by uncaptured calls, never launched on
     std::vector<GenGraph> graphs;   // recorded K-step loops (at most GEN_GRAPHS, least recently used out)
     uint64_t use_clock = 0;
 };
@@ -680,6 +673,9 @@ static void gen_drop_graphs(GenModel* g, const float* scratch) {   // scratch nu
     }
     g->graphs.swap(keep);
 }
+// the handle's scratch pool is about to replace the buffer `old` of a stream it has synced (null: the stream
+// had none yet): the loops recorded over it go first
+static void gen_scratch_replaced(void* g, const float* old) { gen_drop_graphs(static_cast<GenModel*>(g), old); }
 
 // the instance serving a GenFused handle (GenFused::inst): 0 dpkw, 1 dpkw4, 2 dpkn, 3 dpkn4
 #define DPK_FZ_SWITCH(INST, CALL)          \
@@ -726,7 +722,6 @@ static GenModel* gen_new(int D, int H, int J, int L, int cin, int cout, int kind
 }
 
 static int gen_graph_count(const GenModel* g) { return g ? (int)g->graphs.size() : 0; }
-static int gen_spare_kib(const GenModel* g) { return g ? (int)((g->spare.cap * 4) >> 10) : 0; }
 
 static void gen_free(GenModel* g) {
     if (!g) return;
@@ -739,9 +734,6 @@ static void gen_free(GenModel* g) {
     }
     if (g->dev) (void)hipFree(g->dev);
     if (g->devp) (void)hipFree(g->devp);
-    for (auto& s : g->scratch)
-        if (s.p) (void)hipFree(s.p);
-    if (g->spare.p) (void)hipFree(g->spare.p);
     delete g;
 }
 
@@ -796,90 +788,21 @@ static int gen_upload(dpk_handle* h, GenModel* g) {
     return DPK_OK;
 }
 
-// Per-stream scratch of at least n floats (grown after a sync of that stream only: launches on
-// other streams use their own)
-static int gen_scratch(dpk_handle* h, GenModel* g, hipStream_t st, size_t n, float** out) {
-    GenScratch* s = nullptr;
-    for (auto& x : g->scratch)
-        if (x.st == st) s = &x;
-    if (!s) {
-        g->scratch.push_back(GenScratch{st, nullptr, 0});
-        s = &g->scratch.back();
-    }
-    if (s->cap < n) {
-        HIPCHK(h, hipStreamSynchronize(st));
-        gen_drop_graphs(g, s->p);      // loops recorded over the old buffer (their stream has drained)
-        if (s->p) HIPCHK(h, hipFree(s->p));
-        s->p = nullptr;
-        s->cap = 0;
-        HIPCHK(h, hipMalloc(&s->p, n * 4));
-        s->cap = n;
-    }
-    *out = s->p;
-    return DPK_OK;
-}
-
-// Scratch of a captured generic call.  The captured launches keep its address for the graph's life and
-// may replay concurrently with uncaptured calls, so a capture cannot use the stream's scratch: the first
-// captured call of a capturing stream takes the model's spare (allocated by uncaptured calls of at least
-// that size, since nothing can be allocated inside a capture), and every later captured call of that
-// stream in the same capture (sequential graph nodes) shares it.  The buffer belongs to the capture's
-// CapRes and returns to the spare when the graph is destroyed (cap_sweep).
-static void gen_spare_put(dpk_handle* h, float* p, size_t cap) {
-    GenModel* g = h->gen;
-    if (g && (!g->spare.p || g->spare.cap < cap)) {
-        if (g->spare.p) (void)hipFree(g->spare.p);
-        g->spare = GenScratch{nullptr, p, cap};
-    } else {
-        (void)hipFree(p);
-    }
-}
-// uncaptured calls: keep a spare of at least n floats for a later capture (no launch has seen it).  Only a
-// capture needs it, so a failed allocation is not the uncaptured call's failure (ADVICE r05): the error is
-// cleared and the spare left unsized, and a later capture of this size is refused with DPK_E_STATE
-// (gen_scratch_cap).  The spare costs one more scratch-sized buffer per generic handle.
-static void gen_spare_reserve(GenModel* g, size_t n) {
-    if (g->spare.cap >= n) return;
-    if (g->spare.p) (void)hipFree(g->spare.p);
-    g->spare = GenScratch{};
-    float* p = nullptr;
-    if (hipMalloc(&p, n * 4) != hipSuccess) {
-        (void)hipGetLastError();
-        return;
-    }
-    g->spare.p = p;
-    g->spare.cap = n;
-}
-static int gen_scratch_cap(dpk_handle* h, GenModel* g, hipStream_t st, size_t n, float** out, const char* who) {
-    CapRes* c = nullptr;
-    int rc = cap_get(h, st, &c);
-    if (rc) return rc;
-    for (auto& b : c->gen)
-        if (b.st == st) {
-            if (b.cap < n)
-                return fail(h, DPK_E_STATE, std::string(who) + ": the captured calls of one stream share the scratch of "
-                                                               "the capture's first generic call; warm up with the largest "
-                                                               "call before capturing");
-            *out = b.p;
-            return DPK_OK;
-        }
-    if (g->spare.cap < n)
-        return fail(h, DPK_E_STATE, std::string(who) + ": a captured generic-shape call needs " + std::to_string(n) +
-                                        " floats of scratch and the spare holds " + std::to_string(g->spare.cap) +
-                                        "; make the same call once uncaptured before the capture");
-    c->gen.push_back(CapRes::GenBuf{st, g->spare.p, g->spare.cap});
-    g->spare = GenScratch{};
-    *out = c->gen.back().p;
-    return DPK_OK;
-}
-// the scratch of a generic call: the stream's own (uncaptured; the spare grown alongside) or the capture's
-static int gen_scratch_any(dpk_handle* h, GenModel* g, hipStream_t st, bool cap, size_t n, float** out,
-                           const char* who) {
-    if (cap) return gen_scratch_cap(h, g, st, n, out, who);
-    int rc = gen_scratch(h, g, st, n, out);
-    if (rc) return rc;
-    gen_spare_reserve(g, n);
-    return DPK_OK;
+// n floats of scratch for a generic call (call_scratch), a captured call's refusals in floats.  The pool costs
+// one more scratch-sized buffer per generic handle, its spare.
+static int gen_scratch(dpk_handle* h, hipStream_t st, bool cap, size_t n, float** out, const char* who) {
+    ScratchBuf buf;
+    ScratchStatus why;
+    const int rc = call_scratch(h, st, cap, n, who, buf, why);
+    *out = buf.p;
+    if (why == SCRATCH_NO_SPARE)
+        return fail(h, rc, std::string(who) + ": a captured generic-shape call needs " + std::to_string(n) +
+                               " floats of scratch and the spare holds " + std::to_string(buf.cap) +
+                               "; make the same call once uncaptured before the capture");
+    if (why == SCRATCH_SHARED_TOO_SMALL)
+        return fail(h, rc, std::string(who) + ": the captured calls of one stream share the scratch of the capture's "
+                                              "first generic call; warm up with the largest call before capturing");
+    return rc;
 }
 
 static inline unsigned gen_blocks(long long n) { return (unsigned)((n + 255) / 256); }
@@ -1021,66 +944,35 @@ static void gen_temb(GenModel* g, hipStream_t st, const float* tvals, int tstrid
                        W + g->s.d1b, W + g->s.wtp, W + g->s.btp, tvals, tstride, g->s.D, g->s.E, g->s.L, neg, tproj);
 }
 
+// dpk_sample / dpk_eps on a GenFused handle: scratch for the timestep projections ([K][NL][D] of the schedule,
+// per call; [N][NL][D] per pose), the projections, one launch of the instance's sampler
+template <int MODE>
+static int gen_fused_run(dpk_handle* h, const SampleArgs& a, hipStream_t st, bool cap, const char* who) {
+    return profiled(h, st, cap, who, [&]() -> int {
+        gen_fused_launch<MODE>(h->gen, a, st);
+        HIPCHK(h, hipGetLastError());
+        return DPK_OK;
+    });
+}
 static int gen_fused_sample(dpk_handle* h, Sched* sc, const float* x, float* out, float* xs, float* x0s, int N,
                             uint64_t seed, const float* noise, hipStream_t st, bool cap) {
-    GenModel* g = h->gen;
-    GenFused* f = g->fz;
-    const int K = sc->K;
-    const long long n = (long long)N * g->s.J * g->s.cin;
-    float* S = nullptr;          // the schedule's timestep projections [K][NL][D], per call
-    int rc = gen_scratch_any(h, g, st, cap, (size_t)K * gen_fused_tp(f), &S, "dpk_sample");
+    const GenModel* g = h->gen;
+    float* S = nullptr;
+    int rc = gen_scratch(h, st, cap, (size_t)sc->K * gen_fused_tp(g->fz), &S, "dpk_sample");
     if (rc) return rc;
-    gen_fused_temb(f, sc->coef + 5, 6, K, S, st);
-    if (xs) HIPCHK(h, hipMemcpyAsync(xs, x, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
-    SampleArgs a{};
-    a.arena = f->arena;
-    a.coef = sc->coef;
-    a.tproj = S;
-    a.x_in = x;
-    a.x_out = out;
-    a.xs = xs;
-    a.x0s = x0s;
-    a.N = N;
-    a.K = K;
-    a.mask = h->mask;
-    a.pmask = h->pmask;
-    a.eta = sc->eta;
-    a.seed = seed;
-    a.num_layers = g->s.L;
-    a.noise = noise;
-    std::pair<hipEvent_t, hipEvent_t> ev;
-    const bool prof = h->profiling && !cap;
-    if (prof && prof_begin(h, st, ev)) return fail(h, DPK_E_HIP, "dpk_sample: event record");
-    gen_fused_launch<M_SAMPLE>(g, a, st);
-    HIPCHK(h, hipGetLastError());
-    if (prof && prof_end(h, st, ev)) return fail(h, DPK_E_HIP, "dpk_sample: event record");
-    return sched_note_use(h, sc, st, cap);
+    gen_fused_temb(g->fz, sc->coef + 5, 6, sc->K, S, st);
+    if (xs) HIPCHK(h, hipMemcpyAsync(xs, x, (size_t)N * g->s.J * g->s.cin * 4, hipMemcpyDeviceToDevice, st));
+    rc = gen_fused_run<M_SAMPLE>(h, sample_args(h, g->fz->arena, S, sc, x, out, xs, x0s, N, seed, noise), st, cap,
+                                 "dpk_sample");
+    return rc ? rc : sched_note_use(h, sc, st, cap);
 }
-
 static int gen_fused_eps(dpk_handle* h, const float* x, const float* t, float* eps, int N, hipStream_t st, bool cap) {
-    GenModel* g = h->gen;
-    GenFused* f = g->fz;
-    float* S = nullptr;          // per-pose timestep projections [N][NL][D]
-    int rc = gen_scratch_any(h, g, st, cap, (size_t)N * gen_fused_tp(f), &S, "dpk_eps");
+    const GenFused* f = h->gen->fz;
+    float* S = nullptr;
+    const int rc = gen_scratch(h, st, cap, (size_t)N * gen_fused_tp(f), &S, "dpk_eps");
     if (rc) return rc;
     gen_fused_temb(f, t, 1, N, S, st);
-    SampleArgs a{};
-    a.arena = f->arena;
-    a.tproj = S;
-    a.x_in = x;
-    a.x_out = eps;
-    a.N = N;
-    a.K = 1;
-    a.mask = h->mask;
-    a.pmask = h->pmask;
-    a.num_layers = g->s.L;
-    std::pair<hipEvent_t, hipEvent_t> ev;
-    const bool prof = h->profiling && !cap;
-    if (prof && prof_begin(h, st, ev)) return fail(h, DPK_E_HIP, "dpk_eps: event record");
-    gen_fused_launch<M_EPS>(g, a, st);
-    HIPCHK(h, hipGetLastError());
-    if (prof && prof_end(h, st, ev)) return fail(h, DPK_E_HIP, "dpk_eps: event record");
-    return DPK_OK;
+    return gen_fused_run<M_EPS>(h, eps_args(h, f->arena, S, x, eps, N), st, cap, "dpk_eps");
 }
 
 // dpk_sample on the generic path: one forward + DDIM update per step.  Without trajectory outputs or
@@ -1095,7 +987,7 @@ static int gen_sample(dpk_handle* h, Sched* sc, const float* x, float* out, floa
     const long long n = (long long)N * g->s.J * g->s.cin;
     const size_t act = gen_act_floats(g, N), tpf = (size_t)K * g->s.L * g->s.D;
     float* S = nullptr;
-    int rc = gen_scratch_any(h, g, st, cap, act + 2 * (size_t)n + tpf, &S, "dpk_sample");
+    int rc = gen_scratch(h, st, cap, act + 2 * (size_t)n + tpf, &S, "dpk_sample");
     if (rc) return rc;
     float* eps = S + act;
     float* tproj = eps + n;
@@ -1155,60 +1047,53 @@ static int gen_sample(dpk_handle* h, Sched* sc, const float* x, float* out, floa
             g->graphs.push_back(GenGraph{key, ex, ++g->use_clock});
         }
     }
-    std::pair<hipEvent_t, hipEvent_t> ev;
-    const bool prof = h->profiling && !cap;
-    if (prof && prof_begin(h, st, ev)) return fail(h, DPK_E_HIP, "dpk_sample: event record");
-    if (xs) HIPCHK(h, hipMemcpyAsync(xs, x, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
-    if (graphed) {
-        HIPCHK(h, hipMemcpyAsync(xt, x, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
-        HIPCHK(h, hipGraphLaunch(ex, st));
-        HIPCHK(h, hipMemcpyAsync(out, xt, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
-    } else {
-        HIPCHK(h, hipMemcpyAsync(out, x, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
-        body(st, out);
-    }
-    HIPCHK(h, hipGetLastError());
-    if (prof && prof_end(h, st, ev)) return fail(h, DPK_E_HIP, "dpk_sample: event record");
-    return sched_note_use(h, sc, st, cap);
+    rc = profiled(h, st, cap, "dpk_sample", [&]() -> int {
+        if (xs) HIPCHK(h, hipMemcpyAsync(xs, x, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+        if (graphed) {
+            HIPCHK(h, hipMemcpyAsync(xt, x, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+            HIPCHK(h, hipGraphLaunch(ex, st));
+            HIPCHK(h, hipMemcpyAsync(out, xt, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+        } else {
+            HIPCHK(h, hipMemcpyAsync(out, x, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+            body(st, out);
+        }
+        HIPCHK(h, hipGetLastError());
+        return DPK_OK;
+    });
+    return rc ? rc : sched_note_use(h, sc, st, cap);
 }
 
 // dpk_eps on the generic path: per-pose timestep projections, one forward
 static int gen_eps(dpk_handle* h, const float* x, const float* t, float* eps, int N, hipStream_t st, bool cap) {
-    if (!cap) cap_sweep(h);
     if (h->gen->fz) return gen_fused_eps(h, x, t, eps, N, st, cap);
     GenModel* g = h->gen;
-    const size_t act = gen_act_floats(g, N), tpf = (size_t)N * g->s.L * g->s.D;
+    const size_t act = gen_act_floats(g, N);
     float* S = nullptr;
-    int rc = gen_scratch_any(h, g, st, cap, act + tpf, &S, "dpk_eps");
+    const int rc = gen_scratch(h, st, cap, act + (size_t)N * g->s.L * g->s.D, &S, "dpk_eps");
     if (rc) return rc;
     float* tproj = S + act;
-    std::pair<hipEvent_t, hipEvent_t> ev;
-    const bool prof = h->profiling && !cap;
-    if (prof && prof_begin(h, st, ev)) return fail(h, DPK_E_HIP, "dpk_eps: event record");
-    gen_temb(g, st, t, 1, N, tproj);
-    gen_forward(g, st, x, N, tproj, g->s.L * g->s.D, h->mask, h->pmask, eps, S, h->n_cu);
-    HIPCHK(h, hipGetLastError());
-    if (prof && prof_end(h, st, ev)) return fail(h, DPK_E_HIP, "dpk_eps: event record");
-    return DPK_OK;
+    return profiled(h, st, cap, "dpk_eps", [&]() -> int {
+        gen_temb(g, st, t, 1, N, tproj);
+        gen_forward(g, st, x, N, tproj, g->s.L * g->s.D, h->mask, h->pmask, eps, S, h->n_cu);
+        HIPCHK(h, hipGetLastError());
+        return DPK_OK;
+    });
 }
 
 // dpk_pose on the generic path: GCNpose forward (no timestep projection), then xyz / uvxyz
 static int gen_pose(dpk_handle* h, const float* x2d, float* xyz, float* uvxyz, int N, int Hn, int root_mode,
                     hipStream_t st, bool cap) {
-    if (!cap) cap_sweep(h);
     GenModel* g = h->gen;
-    const size_t act = gen_act_floats(g, N), yn = (size_t)N * g->s.J * g->s.cout;
+    const size_t act = gen_act_floats(g, N);
     float* S = nullptr;
-    int rc = gen_scratch_any(h, g, st, cap, act + yn, &S, "dpk_pose");
+    const int rc = gen_scratch(h, st, cap, act + (size_t)N * g->s.J * g->s.cout, &S, "dpk_pose");
     if (rc) return rc;
     float* y = S + act;
-    std::pair<hipEvent_t, hipEvent_t> ev;
-    const bool prof = h->profiling && !cap;
-    if (prof && prof_begin(h, st, ev)) return fail(h, DPK_E_HIP, "dpk_pose: event record");
-    gen_forward(g, st, x2d, N, nullptr, 0, h->mask, h->pmask, y, S, h->n_cu);
-    hipLaunchKernelGGL(dpkg::pose_out, dim3(gen_blocks((long long)N * g->s.J * (g->s.cin + g->s.cout))), dim3(256), 0, st,
-                       x2d, y, N, g->s.J, g->s.cin, g->s.cout, xyz, uvxyz, Hn, root_mode);
-    HIPCHK(h, hipGetLastError());
-    if (prof && prof_end(h, st, ev)) return fail(h, DPK_E_HIP, "dpk_pose: event record");
-    return DPK_OK;
+    return profiled(h, st, cap, "dpk_pose", [&]() -> int {
+        gen_forward(g, st, x2d, N, nullptr, 0, h->mask, h->pmask, y, S, h->n_cu);
+        hipLaunchKernelGGL(dpkg::pose_out, dim3(gen_blocks((long long)N * g->s.J * (g->s.cin + g->s.cout))), dim3(256), 0,
+                           st, x2d, y, N, g->s.J, g->s.cin, g->s.cout, xyz, uvxyz, Hn, root_mode);
+        HIPCHK(h, hipGetLastError());
+        return DPK_OK;
+    });
 }

@@ -110,6 +110,7 @@ struct SampleArgs {
 }  // namespace dpk_shared
 
 #include "dpk_stage.inc"
+#include "dpk_scratch.inc"
 
 #define DPK_P 4
 namespace dpk {
@@ -212,21 +213,8 @@ struct Sched {
     std::vector<std::pair<hipStream_t, hipEvent_t>> uses;   // last launch on each stream
 };
 
-// dpk_eps's per-pose projections [N][NL][D].  Uncaptured calls use one buffer per caller stream:
-// two dpk_eps calls on different streams never share one, and calls on the same stream are ordered
-// by the stream, so a buffer can grow (after a sync of its stream) without racing anyone.  A
-// captured call becomes a graph node that keeps the buffer's address for the graph's life and may
-// replay on any stream, concurrently with other graphs: it takes a buffer of its own, the handle's
-// spare (allocated by the uncaptured calls, since nothing can be allocated inside a capture), and
-// that buffer is pinned until dpk_destroy.
-struct EpsBuf {
-    hipStream_t st = nullptr;
-    float* p = nullptr;
-    int cap = 0;
-};
-
 // What the launches captured in one stream capture (one hipGraph) read by address: the schedules
-// they were captured with, dpk_eps projection buffers (one per capturing stream: the captured
+// they were captured with, scratch buffers (dpk_scratch.inc: one per capturing stream, the captured
 // launches of one stream are sequential graph nodes and share it) and step-split flag slots (one
 // per capturing stream likewise).  A HIP user object retained by the capture's graph drops the
 // graph's reference when the graph and its executable instances are destroyed (host callback, no
@@ -238,16 +226,8 @@ struct CapRes {
     std::atomic<bool> released{false};
     bool tracked = false;                      // a graph retains our user object
     std::vector<Sched*> scheds;
-    std::vector<EpsBuf> eps;                   // per capturing stream
+    std::vector<ScratchBuf> bufs;              // scratch per capturing stream (taken from the pool's spare)
     std::vector<std::pair<hipStream_t, int>> slots;   // flag slot per capturing stream
-    // generic-shape path: the activation scratch of each capturing stream (taken from the model's
-    // spare, which uncaptured generic calls size; dpk_generic.inc gen_scratch_cap)
-    struct GenBuf {
-        hipStream_t st;
-        float* p;
-        size_t cap;   // floats
-    };
-    std::vector<GenBuf> gen;
 };
 static void cap_release_cb(void* p) {
     CapRes* c = static_cast<CapRes*>(p);
@@ -256,9 +236,6 @@ static void cap_release_cb(void* p) {
 }
 
 struct GenModel;   // dpk_generic.inc: the forward for model shapes other than the compiled one
-struct dpk_handle;
-static void gen_spare_put(dpk_handle* h, float* p, size_t cap);   // dpk_generic.inc
-
 struct dpk_handle {
     int device = 0;
     GenModel* gen = nullptr;       // non-null: this handle's shape runs on the generic path
@@ -283,8 +260,7 @@ struct dpk_handle {
     uint64_t weights_gen = 0;      // bumped by every weight/graph upload
     Sched* sched = nullptr;        // current schedule
     std::vector<Sched*> retired;   // replaced schedules not yet known to be unused
-    std::vector<EpsBuf> eps_bufs;  // per stream (uncaptured dpk_eps)
-    EpsBuf eps_spare;              // unused buffer for the next capture's dpk_eps (no stream)
+    ScratchPool pool;              // dpk_eps's projections [N][NL][D] (shipped shape) or the generic path's scratch
     Stage stage;                   // host staging of the weights and the graph (the shipped shape; else gen's)
     Packed pk;                     // the arenas packed from it (dpk::pack_model), as uploaded
     char* arena16 = nullptr;       // device: split-fp16 GEMM weights (gemm mode 1)
@@ -303,26 +279,30 @@ struct dpk_handle {
 #endif
 };
 
-// event pair around a sampler-kernel launch (dpk_profile)
-static int prof_begin(dpk_handle* h, hipStream_t st, std::pair<hipEvent_t, hipEvent_t>& ev) {
-    if (h->ev_free.empty()) {
-        hipEvent_t a, b;
-        if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return DPK_E_HIP;
-        h->ev_free.push_back({a, b});
-    }
-    ev = h->ev_free.back();
-    h->ev_free.pop_back();
-    return hipEventRecord(ev.first, st) == hipSuccess ? DPK_OK : DPK_E_HIP;
-}
-static int prof_end(dpk_handle* h, hipStream_t st, std::pair<hipEvent_t, hipEvent_t>& ev) {
-    if (hipEventRecord(ev.second, st) != hipSuccess) return DPK_E_HIP;
-    h->ev_used.push_back(ev);
-    return DPK_OK;
-}
-
 static int fail(dpk_handle* h, int code, const std::string& msg) {
     if (h) h->err = msg;
     return code;
+}
+
+// `launch` (returns a DPK code) on `st`, between an event pair when the handle is profiling (dpk_profile;
+// never under a capture)
+template <class F>
+static int profiled(dpk_handle* h, hipStream_t st, bool cap, const char* who, F launch) {
+    if (!h->profiling || cap) return launch();
+    if (h->ev_free.empty()) {
+        hipEvent_t a, b;
+        if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess)
+            return fail(h, DPK_E_HIP, std::string(who) + ": event record");
+        h->ev_free.push_back({a, b});
+    }
+    const std::pair<hipEvent_t, hipEvent_t> ev = h->ev_free.back();
+    h->ev_free.pop_back();
+    if (hipEventRecord(ev.first, st) != hipSuccess) return fail(h, DPK_E_HIP, std::string(who) + ": event record");
+    const int rc = launch();
+    if (rc) return rc;
+    if (hipEventRecord(ev.second, st) != hipSuccess) return fail(h, DPK_E_HIP, std::string(who) + ": event record");
+    h->ev_used.push_back(ev);
+    return DPK_OK;
 }
 
 #define HIPCHK(h, expr)                                                                        \
@@ -426,16 +406,8 @@ static void cap_sweep(dpk_handle* h) {
             continue;
         }
         for (Sched* s : c->scheds) --s->pins;
-        for (auto& e : c->eps) {
-            if (!h->eps_spare.p || h->eps_spare.cap < e.cap) {
-                if (h->eps_spare.p) (void)hipFree(h->eps_spare.p);
-                h->eps_spare = EpsBuf{nullptr, e.p, e.cap};
-            } else {
-                (void)hipFree(e.p);
-            }
-        }
+        scratch_release(h->pool, c->bufs);
         for (auto& s : c->slots) slot_put(h, s.second);
-        for (auto& gb : c->gen) gen_spare_put(h, gb.p, gb.cap);
         if (c->refs.fetch_sub(1) == 1) delete c;
     }
     h->caps.swap(keep);
@@ -622,7 +594,79 @@ static int launch_sampler(dpk_handle* h, hipStream_t st, SampleArgs a, bool cap)
     return DPK_OK;
 }
 
+// n floats of scratch for one call (dpk_scratch.inc): the stream's own buffer, the spare grown alongside, or
+// under a capture that capture's.  A captured call that cannot be served returns DPK_E_STATE with `why` and,
+// in `got`, the capacity that fell short; the caller words the refusal (poses in dpk_eps, floats on the
+// generic path).
+static int call_scratch(dpk_handle* h, hipStream_t st, bool cap, size_t n, const char* who, ScratchBuf& got,
+                        ScratchStatus& why) {
+    why = SCRATCH_OK;
+    if (!cap) {
+        got = ScratchBuf{st, scratch_get(h->pool, st, n), n};
+        if (got.p) return DPK_OK;
+        return fail(h, DPK_E_HIP, std::string(who) + ": scratch of " + std::to_string(n) + " floats: " +
+                                      hipGetErrorString(hipGetLastError()));
+    }
+    CapRes* c = nullptr;
+    const int rc = cap_get(h, st, &c);
+    if (rc) return rc;
+    why = scratch_get_captured(h->pool, c->bufs, st, n, got);
+    return why == SCRATCH_OK ? DPK_OK : DPK_E_STATE;
+}
+
+// Launch arguments of one eps / sample / pose call over N poses, for whichever sampler instance `arena` was
+// packed for (the shipped shape's, or a GenFused handle's): tproj per pose, per step of `sc`, or zeros.
+static SampleArgs eps_args(const dpk_handle* h, const float* arena, const float* tproj, const float* x, float* out,
+                           int N) {
+    SampleArgs a{};
+    a.arena = arena;
+    a.tproj = tproj;
+    a.x_in = x;
+    a.x_out = out;
+    a.N = N;
+    a.K = 1;
+    a.mask = h->mask;
+    a.pmask = h->pmask;
+    a.num_layers = h->num_layers;
+    return a;
+}
+static SampleArgs sample_args(const dpk_handle* h, const float* arena, const float* tproj, const Sched* sc,
+                              const float* x, float* out, float* xs, float* x0s, int N, uint64_t seed,
+                              const float* noise) {
+    SampleArgs a = eps_args(h, arena, tproj, x, out, N);
+    a.coef = sc->coef;
+    a.K = sc->K;
+    a.eta = sc->eta;
+    a.xs = xs;
+    a.x0s = x0s;
+    a.seed = seed;
+    a.noise = noise;
+    return a;
+}
+static SampleArgs pose_args(const dpk_handle* h, const float* arena, const float* zeros, const float* x2d, float* xyz,
+                            float* uvxyz, int N, int H, int root_mode) {
+    SampleArgs a = eps_args(h, arena, zeros, x2d, xyz, N);
+    a.uvxyz = uvxyz;
+    a.H = H;
+    a.root_mode = root_mode;
+    return a;
+}
+
 #include "dpk_generic.inc"
+
+// What dpk_eps, dpk_sample and dpk_pose do once their arguments and the handle's state have passed: the
+// per-pose masks cover the N poses (models/GraFormer.py:107-108 broadcasts [N,1,17]), the handle's device is
+// current, and an uncaptured call recycles what destroyed graphs have released.
+static int enter_call(dpk_handle* h, int N, const char* who, hipStream_t st, bool* cap) {
+    if (h->pmask && N > h->pmask_n)
+        return fail(h, DPK_E_INVALID, std::string(who) + ": " + std::to_string(N) + " poses but dpk_set_pose_masks covers " +
+                                          std::to_string(h->pmask_n));
+    HIPCHK(h, hipSetDevice(h->device));
+    const int rc = capturing(h, st, cap);
+    if (rc) return rc;
+    if (!*cap) cap_sweep(h);
+    return DPK_OK;
+}
 
 extern "C" {
 
@@ -663,8 +707,11 @@ int dpk_create(const dpk_config* cfg, dpk_handle** out) {
     h->n_pts = cfg->n_pts;
     h->mask = cfg->n_pts >= 32 ? ~0u : (1u << cfg->n_pts) - 1u;   // every key attends (all-ones src_mask)
     if (compiled) stage_init(h->stage, D, NH, J, cfg->num_layers, cfg->coords_in, cfg->coords_out, kind);
-    else
+    else {
         h->gen = gen_new(cfg->hid_dim, cfg->n_head, cfg->n_pts, cfg->num_layers, cfg->coords_in, cfg->coords_out, kind);
+        h->pool.replaced = gen_scratch_replaced;   // its recorded loops are keyed by scratch address
+        h->pool.ctx = h->gen;
+    }
     if (hipSetDevice(h->device) != hipSuccess ||
         hipStreamCreateWithFlags(&h->aux, hipStreamNonBlocking) != hipSuccess ||
         hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess) {
@@ -704,12 +751,9 @@ void dpk_destroy(dpk_handle* h) {
     // hipFree waits for the device, so in-flight launches finish before their buffers go
     if (h->sched) sched_free(h->sched);
     for (Sched* s : h->retired) sched_free(s);
-    for (auto& b : h->eps_bufs)
-        if (b.p) (void)hipFree(b.p);
-    if (h->eps_spare.p) (void)hipFree(h->eps_spare.p);
+    scratch_free_all(h->pool);
     for (CapRes* c : h->caps) {
-        for (auto& e : c->eps) (void)hipFree(e.p);
-        for (auto& gb : c->gen) (void)hipFree(gb.p);
+        scratch_free(c->bufs);
         // a graph still alive keeps the CapRes object (its callback touches only that)
         if (c->refs.fetch_sub(1) == 1) delete c;
     }
@@ -755,14 +799,6 @@ int dpk_set_pose_masks(dpk_handle* h, const uint32_t* bits_dev, int n) {
     if (bits_dev && n <= 0) return fail(h, DPK_E_INVALID, "dpk_set_pose_masks: n must be positive");
     h->pmask = reinterpret_cast<const unsigned*>(bits_dev);
     h->pmask_n = bits_dev ? n : 0;
-    return DPK_OK;
-}
-
-// per-pose masks cover the launch's N poses (models/GraFormer.py:107-108 broadcasts [N,1,17])
-static int check_pose_masks(dpk_handle* h, int N, const char* who) {
-    if (h->pmask && N > h->pmask_n)
-        return fail(h, DPK_E_INVALID, std::string(who) + ": " + std::to_string(N) + " poses but dpk_set_pose_masks covers " +
-                                          std::to_string(h->pmask_n));
     return DPK_OK;
 }
 
@@ -876,85 +912,30 @@ int dpk_eps(dpk_handle* h, const float* x, const float* t, float* eps, int N, vo
     int rc = check_ready(h);
     if (rc) return rc;
     if (N == 0) return DPK_OK;
-    if ((rc = check_pose_masks(h, N, "dpk_eps"))) return rc;
-    HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     bool cap = false;
-    rc = capturing(h, st, &cap);
-    if (rc) return rc;
+    if ((rc = enter_call(h, N, "dpk_eps", st, &cap))) return rc;
     if (h->gen) return gen_eps(h, x, t, eps, N, st, cap);
-    float* proj = nullptr;
-    if (cap) {
-        // graph nodes keep this buffer: the capture's own for this stream (its captured dpk_eps calls
-        // are sequential nodes and share it), taken from the spare that uncaptured calls size
-        CapRes* c = nullptr;
-        if ((rc = cap_get(h, st, &c))) return rc;
-        EpsBuf* mine = nullptr;
-        for (auto& e : c->eps)
-            if (e.st == st) mine = &e;
-        if (!mine) {
-            if (h->eps_spare.cap < N)
-                return fail(h, DPK_E_STATE, "dpk_eps: a captured call needs a projection buffer of " +
-                                                std::to_string(N) + " poses, and the spare holds " +
-                                                std::to_string(h->eps_spare.cap) +
-                                                "; make an uncaptured dpk_eps call of >= N poses before the capture");
-            c->eps.push_back(EpsBuf{st, h->eps_spare.p, h->eps_spare.cap});
-            h->eps_spare = EpsBuf{};
-            mine = &c->eps.back();
-        } else if (mine->cap < N) {
-            return fail(h, DPK_E_STATE, "dpk_eps: the captured calls of one stream share the buffer of the capture's "
-                                        "first call (" + std::to_string(mine->cap) + " poses); this one has " +
-                                        std::to_string(N) + "; warm up with the largest N before capturing");
-        }
-        proj = mine->p;
-    } else {
-        cap_sweep(h);
-        EpsBuf* buf = nullptr;
-        for (auto& b : h->eps_bufs)
-            if (b.st == st) buf = &b;
-        if (!buf) {
-            h->eps_bufs.push_back(EpsBuf{st, nullptr, 0});
-            buf = &h->eps_bufs.back();
-        }
-        if (buf->cap < N) {
-            // earlier dpk_eps calls on this stream may still read the old buffer
-            HIPCHK(h, hipStreamSynchronize(st));
-            if (buf->p) HIPCHK(h, hipFree(buf->p));
-            buf->p = nullptr;
-            buf->cap = 0;
-            const int cap_new = std::max(N, 64);
-            HIPCHK(h, hipMalloc(&buf->p, (size_t)cap_new * NL * D * 4));
-            buf->cap = cap_new;
-        }
-        proj = buf->p;
-        // keep a spare of at least N poses for a later capture (no launch has seen it: no race)
-        if (h->eps_spare.cap < N) {
-            if (h->eps_spare.p) HIPCHK(h, hipFree(h->eps_spare.p));
-            h->eps_spare = EpsBuf{};
-            const int cap_new = std::max(N, 64);
-            HIPCHK(h, hipMalloc(&h->eps_spare.p, (size_t)cap_new * NL * D * 4));
-            h->eps_spare.cap = cap_new;
-        }
+    // per-pose projections [N][NL][D]; buffers of at least 64 poses (the capacities in poses are whole)
+    constexpr size_t PP = (size_t)NL * D;
+    ScratchBuf buf;
+    ScratchStatus why;
+    if ((rc = call_scratch(h, st, cap, (size_t)(cap ? N : std::max(N, 64)) * PP, "dpk_eps", buf, why))) {
+        if (why == SCRATCH_NO_SPARE)
+            return fail(h, rc, "dpk_eps: a captured call needs a projection buffer of " + std::to_string(N) +
+                                   " poses, and the spare holds " + std::to_string(buf.cap / PP) +
+                                   "; make an uncaptured dpk_eps call of >= N poses before the capture");
+        if (why == SCRATCH_SHARED_TOO_SMALL)
+            return fail(h, rc, "dpk_eps: the captured calls of one stream share the buffer of the capture's "
+                               "first call (" + std::to_string(buf.cap / PP) + " poses); this one has " +
+                                   std::to_string(N) + "; warm up with the largest N before capturing");
+        return rc;
     }
-    hipLaunchKernelGGL(temb_kernel, dim3(N), dim3(256), 0, st, h->temb, t, 1, proj);
+    hipLaunchKernelGGL(temb_kernel, dim3(N), dim3(256), 0, st, h->temb, t, 1, buf.p);
     HIPCHK(h, hipGetLastError());
-    SampleArgs a{};
-    a.arena = h->arena;
-    a.coef = nullptr;     // unused in eps mode
-    a.tproj = proj;
-    a.x_in = x;
-    a.x_out = eps;
-    a.N = N;
-    a.K = 1;
-    a.mask = h->mask;
-    a.pmask = h->pmask;
-    a.num_layers = h->num_layers;
-    const bool prof = h->profiling && !cap;
-    std::pair<hipEvent_t, hipEvent_t> ev;
-    if (prof && prof_begin(h, st, ev)) return fail(h, DPK_E_HIP, "dpk_eps: event record");
-    if ((rc = launch_sampler<M_EPS>(h, st, a, cap))) return rc;
-    if (prof && prof_end(h, st, ev)) return fail(h, DPK_E_HIP, "dpk_eps: event record");
-    return DPK_OK;
+    return profiled(h, st, cap, "dpk_eps", [&] {
+        return launch_sampler<M_EPS>(h, st, eps_args(h, h->arena, buf.p, x, eps, N), cap);
+    });
 }
 
 int dpk_sample(dpk_handle* h, const float* x, float* out, float* xs, float* x0s, int N, uint64_t seed,
@@ -973,34 +954,13 @@ int dpk_sample_noise(dpk_handle* h, const float* x, float* out, float* xs, float
     if (N == 0) return DPK_OK;
     if (!h->gen && sc->tps_gen != h->weights_gen)
         return fail(h, DPK_E_STATE, "dpk_sample: schedule projections are stale");
-    if ((rc = check_pose_masks(h, N, "dpk_sample"))) return rc;
-    HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     bool cap = false;
-    rc = capturing(h, st, &cap);
-    if (rc) return rc;
-    if (!cap) {
-        cap_sweep(h);
-        sched_sweep(h);
-    }
+    if ((rc = enter_call(h, N, "dpk_sample", st, &cap))) return rc;
+    if (!cap) sched_sweep(h);
     if (h->gen) return gen_sample(h, sc, x, out, xs, x0s, N, seed, noise, st, cap);
     if (xs) HIPCHK(h, hipMemcpyAsync(xs, x, (size_t)N * PE * 4, hipMemcpyDeviceToDevice, st));
-    SampleArgs a{};
-    a.noise = noise;
-    a.arena = h->arena;
-    a.coef = sc->coef;
-    a.tproj = sc->tps;
-    a.x_in = x;
-    a.x_out = out;
-    a.xs = xs;
-    a.x0s = x0s;
-    a.N = N;
-    a.K = sc->K;
-    a.mask = h->mask;
-    a.pmask = h->pmask;
-    a.eta = sc->eta;
-    a.seed = seed;
-    a.num_layers = h->num_layers;
+    SampleArgs a = sample_args(h, h->arena, sc->tps, sc, x, out, xs, x0s, N, seed, noise);
 #if DPK_TRACE
     if (h->trace_step >= 0) {
         const size_t len = (size_t)((N + P - 1) / P) * NW * TRACE_SLOTS;
@@ -1014,12 +974,8 @@ int dpk_sample_noise(dpk_handle* h, const float* x, float* out, float* xs, float
     a.trace = h->trace_step >= 0 ? h->trace : nullptr;
     a.trace_step = h->trace_step;
 #endif
-    const bool prof = h->profiling && !cap;
-    std::pair<hipEvent_t, hipEvent_t> ev;
-    if (prof && prof_begin(h, st, ev)) return fail(h, DPK_E_HIP, "dpk_sample: event record");
-    if ((rc = launch_sampler<M_SAMPLE>(h, st, a, cap))) return rc;
-    if (prof && prof_end(h, st, ev)) return fail(h, DPK_E_HIP, "dpk_sample: event record");
-    return sched_note_use(h, sc, st, cap);
+    rc = profiled(h, st, cap, "dpk_sample", [&] { return launch_sampler<M_SAMPLE>(h, st, a, cap); });
+    return rc ? rc : sched_note_use(h, sc, st, cap);
 }
 
 int dpk_pose(dpk_handle* h, const float* x2d, float* xyz, float* uvxyz, int N, int H, int root_mode,
@@ -1030,32 +986,13 @@ int dpk_pose(dpk_handle* h, const float* x2d, float* xyz, float* uvxyz, int N, i
     int rc = check_ready(h, 1);
     if (rc) return rc;
     if (N == 0) return DPK_OK;
-    if ((rc = check_pose_masks(h, N, "dpk_pose"))) return rc;
-    HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     bool cap = false;
-    rc = capturing(h, st, &cap);
-    if (rc) return rc;
+    if ((rc = enter_call(h, N, "dpk_pose", st, &cap))) return rc;
     if (h->gen) return gen_pose(h, x2d, xyz, uvxyz, N, H, root_mode, st, cap);
-    SampleArgs a{};
-    a.arena = h->arena;
-    a.num_layers = h->num_layers;
-    a.tproj = h->tproj_zero;   // zeros
-    a.x_in = x2d;
-    a.x_out = xyz;
-    a.uvxyz = uvxyz;
-    a.N = N;
-    a.K = 1;
-    a.H = H;
-    a.root_mode = root_mode;
-    a.mask = h->mask;
-    a.pmask = h->pmask;
-    const bool prof = h->profiling && !cap;
-    std::pair<hipEvent_t, hipEvent_t> ev;
-    if (prof && prof_begin(h, st, ev)) return fail(h, DPK_E_HIP, "dpk_pose: event record");
-    if ((rc = launch_sampler<M_POSE>(h, st, a, cap))) return rc;
-    if (prof && prof_end(h, st, ev)) return fail(h, DPK_E_HIP, "dpk_pose: event record");
-    return DPK_OK;
+    return profiled(h, st, cap, "dpk_pose", [&] {
+        return launch_sampler<M_POSE>(h, st, pose_args(h, h->arena, h->tproj_zero, x2d, xyz, uvxyz, N, H, root_mode), cap);
+    });
 }
 
 int dpk_set_gemm_mode(dpk_handle* h, int mode) {
@@ -1143,8 +1080,11 @@ int dpk_debug_resources(dpk_handle* h, int* out, int n) {
         tracked += c->tracked ? 1 : 0;
         released += (c->tracked && c->released.load()) ? 1 : 0;
     }
+    // the pool's spare: in poses of dpk_eps projections on the shipped shape, in KiB on the generic path
+    const size_t spare = h->pool.spare.cap;
     const int v[8] = {(int)h->caps.size(), tracked, released, (int)h->slot_free.size(), retired,
-                      h->eps_spare.cap, gen_graph_count(h->gen), gen_spare_kib(h->gen)};
+                      h->gen ? 0 : (int)(spare / ((size_t)NL * D)), gen_graph_count(h->gen),
+                      h->gen ? (int)((spare * 4) >> 10) : 0};
     for (int i = 0; i < n && i < 8; ++i) out[i] = v[i];
     return DPK_OK;
 }

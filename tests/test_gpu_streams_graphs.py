@@ -506,3 +506,32 @@ def test_sweep_while_another_thread_captures(dev, monkeypatch):
     del gA
     mA.close()
     mB.close()
+
+
+def test_spare_is_reported_in_poses_or_kib_by_handle_kind(dev):
+    """dpk_debug_resources reports the handle's spare scratch (what the next capture would take) in the
+    units of the handle's kind: on the shipped shape as dpk_eps poses (the spare is sized by the largest
+    uncaptured call, at least 64 poses, and never shrinks) with generic_spare_kib 0; on a generic-shape
+    handle as KiB of activation scratch with eps_spare_poses 0."""
+    from types import SimpleNamespace as ns
+
+    m = _model(dev)
+    x = torch.from_numpy(synthetic_batch(70, seed=21)[0]).to(dev)
+    mask = torch.ones(1, 1, 17, dtype=torch.bool, device=dev)
+    t = torch.full((70,), 5.0, device=dev)
+    m(x, mask, t, 0)
+    r = m.debug_resources()
+    assert r["eps_spare_poses"] == 70 and r["generic_spare_kib"] == 0, r
+    m(x[:10].contiguous(), mask, t[:10], 0)
+    assert m.debug_resources()["eps_spare_poses"] == 70
+    m.close()
+    # hid 8 / 2 heads, coords 9 -> 9 on a 17-joint chain: the per-op generic path (no sampler instance fits)
+    cfg = ns(model=ns(hid_dim=8, emd_dim=8, coords_dim=[9, 9], num_layer=2, n_head=2, dropout=0.25, n_pts=17))
+    g = HipGCNdiff(adj_mx_from_edges(17, tuple((i, i + 1) for i in range(16))), cfg, device=dev)
+    g.load_state_dict(synthetic_state_dict(hid=8, n_layers=2, n_pts=17, coords=(9, 9)))
+    xg = torch.randn(8, 17, 9, generator=torch.Generator().manual_seed(8)).to(dev)
+    g(xg, mask, torch.full((8,), 5.0, device=dev), 0)
+    torch.cuda.synchronize()
+    r = g.debug_resources()
+    assert r["eps_spare_poses"] == 0 and r["generic_spare_kib"] > 0, r
+    g.close()
