@@ -117,6 +117,15 @@ namespace dpk {
 #include "dpk_sampler.inc"
 #include "dpk_genfused.inc"
 }  // namespace dpk
+// The same 4-pose tile on 8 waves, two per SIMD (dpk_layout.inc DPK_NW): each SIMD's GEMM column tiles split
+// between its two waves, the per-pose phases split between the two waves of a pose as in the 2-pose tile.
+// At most 256 registers per lane; dpk_set_tile_waves chooses between this instance and dpk per GEMM mode.
+#define DPK_NW 8
+namespace dpk8 {
+#include "dpk_sampler.inc"
+#include "dpk_genfused.inc"
+}  // namespace dpk8
+#undef DPK_NW
 #undef DPK_P
 #define DPK_P 2
 namespace dpk2 {
@@ -266,6 +275,7 @@ struct dpk_handle {
     char* arena16 = nullptr;       // device: split-fp16 GEMM weights (gemm mode 1)
     char* arenabf = nullptr;       // device: bf16 GEMM weights (gemm mode 2), same layout
     int gemm_mode = 0;             // 0: fp32 MFMA, 1: 3x fp16-split MFMA, 2: bf16 MFMA (dpk_set_gemm_mode)
+    int tile_waves = 0;            // dpk_set_tile_waves: 4 or 8 waves on the 4-pose tiles of dpk_sample; 0 the mode's default
     bool have_graph = false, have_weights = false;
     unsigned mask = (1u << J) - 1u;
     const unsigned* pmask = nullptr;   // dpk_set_pose_masks: caller-owned device array
@@ -528,13 +538,37 @@ static int split_slot_hold(dpk_handle* h, int slot, hipStream_t st) {
     return DPK_OK;
 }
 
+// Waves on the 4-pose tiles of a dpk_sample launch: the handle's choice (dpk_set_tile_waves), else the GEMM
+// mode's default (the paired measurements per mode).
+// fp32 +1.2 %, bf16 (config 3) +1.5 % on 8 waves, every one of 5 interleaved pairs faster; f16x3 -6 %: both
+// waves of a SIMD split the same activation rows into fp16 hi + lo (profiles/w8_ab_*.txt)
+constexpr int TILE_WAVES_DEFAULT[3] = {8, 4, 8};   // fp32, f16x3, bf16
+// A graph outside the compiled H36M pattern (the dense Chebyshev path) defaults to 4 waves in every mode: its
+// 8-wave kernels do not fit 256 registers (442-532 spilled VGPRs, profiles/w8_resource_usage.txt; the 4-wave
+// dense kernels already fill 512) and were not measured; they run on explicit request only.
+static int tile_waves(const dpk_handle* h) {
+    if (h->tile_waves) return h->tile_waves;
+    return h->pk.sparse ? TILE_WAVES_DEFAULT[h->gemm_mode] : 4;
+}
+
 // One launch of the sampler kernel with tile size PT (4: dpk, 2: dpk2) for the handle's graph
 // pattern and GEMM mode.
 template <int MODE, int PT>
 static void launch_tiles(dpk_handle* h, int blocks, size_t shmem, hipStream_t st, const SampleArgs& a) {
     const char* a16 = h->gemm_mode == 2 ? h->arenabf : h->arena16;
-    if constexpr (PT == 4) dpk::launch_sample<MODE>(h->pk.sparse, h->gemm_mode, blocks, shmem, st, a, h->arena, a16);
-    else dpk2::launch_sample<MODE>(h->pk.sparse, h->gemm_mode, blocks, shmem, st, a, h->arena, a16);
+    if constexpr (PT == 4) {
+        // every 4-pose tile of a dpk_sample launch, step-split halves included, on one instance; dpk_eps and
+        // dpk_pose stay on 4 waves
+        if constexpr (MODE == M_SAMPLE) {
+            if (tile_waves(h) == 8) {
+                dpk8::launch_sample<MODE>(h->pk.sparse, h->gemm_mode, blocks, shmem, st, a, h->arena, a16);
+                return;
+            }
+        }
+        dpk::launch_sample<MODE>(h->pk.sparse, h->gemm_mode, blocks, shmem, st, a, h->arena, a16);
+    } else {
+        dpk2::launch_sample<MODE>(h->pk.sparse, h->gemm_mode, blocks, shmem, st, a, h->arena, a16);
+    }
 }
 
 // The sampler over a.N poses.  One 4-pose workgroup per CU per round; a partial last round of r
@@ -721,6 +755,11 @@ int dpk_create(const dpk_config* cfg, dpk_handle** out) {
         return DPK_E_HIP;
     }
     h->n_cu = std::max(h->n_cu, 1);
+    // DPK_TILE_WAVES=0/4/8: the initial tile instance (A/B timing)
+    if (const char* tw = getenv("DPK_TILE_WAVES")) {
+        const int v = atoi(tw);
+        if (v == 0 || v == 4 || v == 8) h->tile_waves = v;
+    }
     // DPK_TAIL_SPLIT=0/1/2: the initial tail plan (A/B timing); trace builds stamp per block id
     if (const char* ts = getenv("DPK_TAIL_SPLIT")) h->tail_plan = std::min(std::max(atoi(ts), 0), 2);
     if (DPK_TRACE) h->tail_plan = 0;
@@ -963,7 +1002,7 @@ int dpk_sample_noise(dpk_handle* h, const float* x, float* out, float* xs, float
     SampleArgs a = sample_args(h, h->arena, sc->tps, sc, x, out, xs, x0s, N, seed, noise);
 #if DPK_TRACE
     if (h->trace_step >= 0) {
-        const size_t len = (size_t)((N + P - 1) / P) * NW * TRACE_SLOTS;
+        const size_t len = (size_t)((N + P - 1) / P) * tile_waves(h) * TRACE_SLOTS;
         if (h->trace_len < len) {
             if (h->trace) HIPCHK(h, hipFree(h->trace));
             HIPCHK(h, hipMalloc(&h->trace, len * 8));
@@ -1000,6 +1039,16 @@ int dpk_set_gemm_mode(dpk_handle* h, int mode) {
     if (mode < 0 || mode > 2)
         return fail(h, DPK_E_INVALID, "dpk_set_gemm_mode: mode must be 0 (fp32), 1 (3xfp16) or 2 (bf16)");
     h->gemm_mode = mode;
+    return DPK_OK;
+}
+
+int dpk_set_tile_waves(dpk_handle* h, int waves) {
+    if (!h) return DPK_E_INVALID;
+    if (waves != 0 && waves != 4 && waves != 8)
+        return fail(h, DPK_E_INVALID, "dpk_set_tile_waves: waves must be 0 (the GEMM mode's default), 4 or 8");
+    if (waves == 8 && h->gen)
+        return fail(h, DPK_E_UNSUPPORTED, "dpk_set_tile_waves: the 8-wave tile is compiled for hid 96 / 4 heads / 17 joints");
+    h->tile_waves = waves;
     return DPK_OK;
 }
 

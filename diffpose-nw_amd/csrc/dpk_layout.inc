@@ -31,11 +31,19 @@ constexpr bool HALF_MODES = D == 96 && NH == 4;
 
 // workgroup tile.  DPK_P (poses per workgroup) is set by the including file: 4 for the main sampler (one
 // workgroup per CU), 2 for the half-size tail tiles that balance the last round of a batch (launch_sampler)
-// and for the width-128 instances.  Both run one workgroup per CU, 4 waves (one per SIMD).
+// and for the width-128 instances.  Both run one workgroup per CU, 4 waves (one per SIMD).  DPK_NW 8 (4-pose
+// tiles of the shipped shape only, namespace dpk8): two waves per SIMD on the same tile; waves w and w + 4
+// share a SIMD and split its GEMM column tiles, waves 2p and 2p + 1 share pose p in the per-pose phases.
 constexpr int P = DPK_P;     // poses per workgroup
 constexpr int R = P * J;     // 68 (34) rows
 static_assert(P == 4 || P == 2, "4 or 2 poses per workgroup");
-constexpr int NW = 4;        // waves per workgroup
+#ifdef DPK_NW
+constexpr int NW = DPK_NW;   // waves per workgroup
+#else
+constexpr int NW = 4;
+#endif
+static_assert(NW == 4 || (NW == 8 && P == 4), "4 waves, or 8 on a 4-pose tile");
+constexpr int NSUB = NW / 4; // waves per SIMD: the GEMM roles are those of wave & 3, sub-wave wave >> 2
 constexpr int NT = 64 * NW;  // threads
 // LDS row strides ≡ 40 (mod 64) dwords: conflict-free b128 A reads and epilogue writes
 constexpr int stride40(int n) { return n + (104 - n % 64) % 64; }

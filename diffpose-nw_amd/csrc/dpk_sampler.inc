@@ -17,7 +17,23 @@ struct NoHook {
 #define DPK_PRE_MID 14   // fp32 GEMM B prefetch issued right behind the preceding phase's MFMAs: 2 O (attention's
                          // score MFMAs), 4 fc1 (graph1's), 8 C1 (graph2's)
 #endif
-#define DPK_MID(bit) ((DPK_PRE_MID & (bit)) != 0)
+// 8 waves, per GEMM mode (_W8 fp32, _W8F f16x3, _W8B bf16; DPK_MID / DPK_LATE are used in sample_kernel only,
+// where G16 is the GEMM mode).  fp32 keeps the 4-wave placement (paired A/B: +1.2 % over 4 waves, +0.5 % with
+// the placement below).  The half-width modes keep only fc1's there: O's and C1's, held across attention and
+// graph2 + cheb_prep, pushed the f16x3 kernel past its 256 registers, and bf16 measured faster without them
+// (+1.5 % against +1.2 %: the SIMD's other wave covers their latency); profiles/w8_ab_placement.txt
+#ifndef DPK_PRE_MID_W8
+#define DPK_PRE_MID_W8 DPK_PRE_MID
+#endif
+#ifndef DPK_PRE_MID_W8F
+#define DPK_PRE_MID_W8F 4
+#endif
+#ifndef DPK_PRE_MID_W8B
+#define DPK_PRE_MID_W8B 4
+#endif
+#define DPK_W8SEL(a, f, b) (G16 == 0 ? (a) : G16 == 1 ? (f) : (b))
+#define DPK_MID(bit) \
+    (((NSUB == 2 ? DPK_W8SEL(DPK_PRE_MID_W8, DPK_PRE_MID_W8F, DPK_PRE_MID_W8B) : DPK_PRE_MID) & (bit)) != 0)
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -255,10 +271,11 @@ enum { TM_NONE = 0, TM_VALU = 1, TM_MFMA4 = 2 };
 // is the A operand, the activation fragment the B operand; both registers are unchanged), so
 // lane l ends up with 4 consecutive COLUMNS 4*(l>>4)..+3 of row l&15 and the epilogue moves
 // one 16-byte vector per tile (ds_write_b128 / ds_read_b128) instead of four 4-byte ones.
-template <int NR, int NCW, int TM, int TR, int KB, bool TRANS = true>
+// NQO: the tail tiles among the NCW (default: the first half, rounded up).
+template <int NR, int NCW, int TM, int TR, int KB, bool TRANS = true, int NQO = (NCW + 1) / 2>
 struct GemmTile {
     static constexpr int TA = TM == TM_VALU ? TR : 1;    // tail A fragments per ring slot
-    static constexpr int NQ = TM == TM_MFMA4 ? (NCW + 1) / 2 : 1;
+    static constexpr int NQ = TM == TM_MFMA4 ? NQO : 1;
     f32x4 acc[NR][NCW];
     float tl[NCW][TA];      // TM_VALU: tail partial sums over this lane's k's
     f32x4 tacc[NQ];         // TM_MFMA4: 4x4x1 accumulators
@@ -318,8 +335,14 @@ struct BPre {
 // Wave roles in the workgroup GEMM: column half ch(w) and index within the pair of waves that
 // share it, pr(w).  68 rows: wave w = row tiles 2*(w>>1)+{0,1} of column half w&1; 34 rows:
 // row tile w&1 of column half w>>1.
+// 8 waves (NSUB = 2): waves w and w + 4 run on one SIMD and share the role of wave w & 3; they split its
+// column tiles (in the rotated local order) into [0, NCW/2) for sub-wave 0 and [NCW/2, NCW) for sub-wave 1,
+// each with the tail rows of those of its tiles that are tail tiles (local index < ceil(NCW/2)).  Every
+// output element is still one k-ordered MFMA chain: the GEMM outputs are bitwise those of 4 waves.
 __device__ __forceinline__ int gemm_ch(int wave) { return R == 68 ? (wave & 1) : (wave >> 1); }
-__device__ __forceinline__ int gemm_pr(int wave) { return R == 68 ? (wave >> 1) : (wave & 1); }
+__device__ __forceinline__ int gemm_pr(int wave) { return R == 68 ? (NSUB == 1 ? wave >> 1 : (wave & 3) >> 1) : (wave & 1); }
+// column tiles of the sub-wave holding the most, of a role's N: what a prefetch struct is sized for
+constexpr int sub_max(int n) { return NSUB == 1 ? n : n - n / 2; }
 
 // Column rotation of wave `wave` within its column half (TM_MFMA4 tail split, see GemmTile).
 template <int NCW>
@@ -336,16 +359,35 @@ __device__ __forceinline__ void tile_offsets(int (&soff)[NCW], const BSrc& s, in
 }
 
 template <int NC, int KB, int NPRE = 2>
-__device__ __forceinline__ BPre<NC / 2> gemm_prefetch(const float* Bp, int wave, int lane) {
-    constexpr int NCW = NC / 2;
+__device__ __forceinline__ BPre<sub_max(NC / 2)> gemm_prefetch(const float* Bp, int wave, int lane) {
+    constexpr int NCW = NC / 2, NP = sub_max(NCW);
     const BSrc s = bsrc<NC, KB>(Bp, gemm_ch(wave) * NCW, lane);
-    int soff[NCW];
-    tile_offsets<NCW, KB>(soff, s, col_rot<NCW>(wave));
-    BPre<NCW> pre;
+    if constexpr (NSUB == 1) {
+        int soff[NCW];
+        tile_offsets<NCW, KB>(soff, s, col_rot<NCW>(wave));
+        BPre<NCW> pre;
 #pragma unroll
-    for (int c = 0; c < NCW; ++c) {
-        pre.b0[c] = bload(s, soff[c], 0);
-        pre.b1[c] = (KB > 1 && NPRE > 1) ? bload(s, soff[c], 1) : f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int c = 0; c < NCW; ++c) {
+            pre.b0[c] = bload(s, soff[c], 0);
+            pre.b1[c] = (KB > 1 && NPRE > 1) ? bload(s, soff[c], 1) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        return pre;
+    }
+    // the sub-wave's first local tile and tile count (wave-uniform)
+    const int c0 = NSUB == 1 ? 0 : (wave >> 2) * (NCW / 2), nown = NSUB == 1 ? NCW : (wave >> 2 ? NCW - NCW / 2 : NCW / 2);
+    const int rot = col_rot<NCW>(wave);
+    BPre<NP> pre;
+#pragma unroll
+    for (int c = 0; c < NP; ++c) {
+        const int cc = c0 + c + rot;
+        const int toff = s.voff + s.sbase + (cc >= NCW ? cc - NCW : cc) * KB * 1024;
+        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+        pre.b0[c] = z;
+        pre.b1[c] = z;
+        if (NSUB == 1 || c < nown) {
+            pre.b0[c] = bload(s, toff, 0);
+            if constexpr (KB > 1 && NPRE > 1) pre.b1[c] = bload(s, toff, 1);
+        }
     }
     return pre;
 }
@@ -355,7 +397,17 @@ __device__ __forceinline__ BPre<NC / 2> gemm_prefetch(const float* Bp, int wave,
                          // 1 QKV (after LN0), 2 O (after attention), 4 fc1 (after LN1+graph1), 8 C1 (after
                          // graph2+cheb_prep), 16 C2 (after cheb_prep2)
 #endif
-#define DPK_LATE(bit) ((DPK_PRE_LATE & (bit)) != 0)
+#ifndef DPK_PRE_LATE_W8
+#define DPK_PRE_LATE_W8 DPK_PRE_LATE
+#endif
+#ifndef DPK_PRE_LATE_W8F
+#define DPK_PRE_LATE_W8F 15
+#endif
+#ifndef DPK_PRE_LATE_W8B
+#define DPK_PRE_LATE_W8B 15
+#endif
+#define DPK_LATE(bit) \
+    (((NSUB == 2 ? DPK_W8SEL(DPK_PRE_LATE_W8, DPK_PRE_LATE_W8F, DPK_PRE_LATE_W8B) : DPK_PRE_LATE) & (bit)) != 0)
 #ifndef DPK_FC1_NPRE
 #define DPK_FC1_NPRE 2   // fp32 fc1: k-blocks of B prefetched ahead of the GEMM
 #endif
@@ -428,11 +480,19 @@ __device__ __forceinline__ float tproj_at(const EpiArgs& e, int row, int col, fl
 // XS2: k-blocks 0 .. 2S-1 of A come from AX (row stride ldx) instead of A: the Chebyshev GEMMs'
 // T0 = x block is read where x lives (cheb_prep XSKIP).  Those k-blocks are loaded only by the
 // prologue and the peeled first ring pass, so the choice is compile-time.
-template <int NR, int NCW, int TM, int TR, int NC, int KB, int MODE, bool XS2 = false, int NPRE = 2>
+// C0, NCS (8 waves): the wave computes the local tiles [C0, C0 + NCS) of the role's NCW0 (in the rotated
+// order), and the tail rows of those of them that are tail tiles (local index < ceil(NCW0/2)).
+template <int NR, int NCW0, int TM0, int TR, int NC, int KB, int MODE, bool XS2 = false, int NPRE = 2, int C0 = 0,
+          int NCS = NCW0, int NPW = NCW0>
 __device__ __forceinline__ void gemm_wave(const float* A, int lda, const float* Bp, int rt0, int ct0, int rot,
                                           int trow0, bool tail_dup, int lane, const EpiArgs& e,
-                                          const BPre<NCW>& pre, const float* AX = nullptr, int ldx = 0) {
-    using T = GemmTile<NR, NCW, TM, TR, KB>;
+                                          const BPre<NPW>& pre, const float* AX = nullptr, int ldx = 0) {
+    constexpr int NCW = NCS;                       // the wave's own tiles: local tile C0 + c
+    constexpr int NQF = (NCW0 + 1) / 2;            // tail tiles of the role
+    constexpr int TQ = NQF - C0 < 0 ? 0 : (NQF - C0 > NCS ? NCS : NQF - C0);   // ... of this wave
+    constexpr int TM = (TM0 == TM_MFMA4 && TQ == 0) ? TM_NONE : TM0;
+    static_assert(C0 >= 0 && NCS >= 1 && C0 + NCS <= NCW0 && NPW >= NCS, "sub-wave tile range");
+    using T = GemmTile<NR, NCW, TM, TR, KB, true, TQ>;
     constexpr int TA = T::TA, NQ = T::NQ;
     static_assert(KB == 1 || KB % 2 == 0, "k-blocks in pairs");
     lane = opaque(lane);
@@ -452,7 +512,7 @@ __device__ __forceinline__ void gemm_wave(const float* A, int lda, const float* 
     }
     int xoff[NR], xtoff = 0;
     if constexpr (XS2) {
-        static_assert(TM == TM_MFMA4, "XS2: 4x4x1 tail rows");
+        static_assert(TM0 == TM_MFMA4, "XS2: 4x4x1 tail rows");
 #pragma unroll
         for (int i = 0; i < NR; ++i) xoff[i] = ((rt0 + i) * 16 + rl) * ldx + kq;
         xtoff = (trow0 + (lane & 3)) * ldx + kq;
@@ -460,8 +520,8 @@ __device__ __forceinline__ void gemm_wave(const float* A, int lda, const float* 
     int gcol[NCW];                                  // global column tile of local tile c (uniform)
 #pragma unroll
     for (int c = 0; c < NCW; ++c) {
-        const int cc = c + rot;
-        gcol[c] = ct0 + (cc >= NCW ? cc - NCW : cc);
+        const int cc = C0 + c + rot;
+        gcol[c] = ct0 + (cc >= NCW0 ? cc - NCW0 : cc);
     }
     // bias (and sample-mode temb projection) of this lane's 4 output columns per tile, and of the
     // tail tiles (TM_MFMA4: after the k-slice reduce-scatter lane l holds tail row l&3, column tcol
@@ -471,7 +531,12 @@ __device__ __forceinline__ void gemm_wave(const float* A, int lda, const float* 
     // cover their L2 latency.
     const BSrc src = bsrc<NC, KB>(Bp, ct0, lane);
     int soff[NCW];
-    tile_offsets<NCW, KB>(soff, src, rot);
+    if constexpr (NCS == NCW0) {
+        tile_offsets<NCW, KB>(soff, src, rot);
+    } else {
+#pragma unroll
+        for (int c = 0; c < NCW; ++c) soff[c] = src.voff + src.sbase + (gcol[c] - ct0) * KB * 1024;
+    }
     const int tcol = 4 * ((lane >> 2) & 3) + (lane >> 4);
     f32x4 bias4[NCW], tp4[NCW];
     float tbias[NQ], ttp[NQ];
@@ -514,7 +579,7 @@ __device__ __forceinline__ void gemm_wave(const float* A, int lda, const float* 
         if (XS2 && kb < KBX) {
 #pragma unroll
             for (int i = 0; i < NR; ++i) as[st][i] = *reinterpret_cast<const f32x4*>(AX + xoff[i] + kb * 16);
-            ts[st][0] = *reinterpret_cast<const f32x4*>(AX + xtoff + kb * 16);
+            if constexpr (TM != TM_NONE) ts[st][0] = *reinterpret_cast<const f32x4*>(AX + xtoff + kb * 16);
         } else {
             g.loadA(as[st], ts[st], A, kb);
         }
@@ -529,11 +594,11 @@ __device__ __forceinline__ void gemm_wave(const float* A, int lda, const float* 
     // (ct0 + c - (rot ? NCW - R0 : 0)): two per-row VGPR bases, and every tile's offset from its base
     // is the compile-time c * 16 floats (the store's immediate field) instead of a spilled SGPR tile
     // offset read back and added per store
-    constexpr int R0 = (NCW + 1) / 2;
+    constexpr int R0 = (NCW0 + 1) / 2;
     auto tile_ptr = [&](int i, int c) -> float* {
         const int row = (rt0 + i) * 16 + rl;
         float* rb = e.dst + row * e.ldd + kq + ct0 * 16;
-        return (c < NCW - R0 ? rb + rot * 16 : rb - (rot ? (NCW - R0) * 16 : 0)) + c * 16;
+        return (C0 + c < NCW0 - R0 ? rb + rot * 16 : rb - (rot ? (NCW0 - R0) * 16 : 0)) + (C0 + c) * 16;
     };
     f32x4 old[NR][NCW];
     float oldt[NQ];
@@ -630,7 +695,7 @@ __device__ __forceinline__ void gemm_wave(const float* A, int lda, const float* 
             // R): with the whole computation under the branch, LLVM sank the last tile's bias load
             // (issued before the k-loop) into it, so the waves that store waited out an L2 round trip
             // in the epilogue of QKV, O and gconv_input while their partners went on to the barrier
-            const bool skip = (q == NQ - 1 && tail_dup) || row >= R;
+            const bool skip = (C0 + q == NQF - 1 && tail_dup) || row >= R;
             const int col = gcol[q] * 16 + tcol;
             const float tp = MODE == E_CHEB1 ? tproj_at(e, min(row, R - 1), col, ttp[q]) : 0.f;
             float val = epi_value<MODE>(v, tbias[q], tp, RES ? oldt[q] : 0.f);
@@ -646,15 +711,25 @@ __device__ __forceinline__ void gemm_wave(const float* A, int lda, const float* 
 // half on 4x4x1 MFMAs, split between the half's two waves (rotated column order for w>>1 = 1).
 template <int NC, int KB, int MODE, bool XS2 = false, int NPRE = 2>
 __device__ __forceinline__ void gemm_wg(const float* A, int lda, const float* Bp, int wave, int lane,
-                                        const EpiArgs& e, const BPre<NC / 2>& pre,
+                                        const EpiArgs& e, const BPre<sub_max(NC / 2)>& pre,
                                         const float* AX = nullptr, int ldx = 0) {
     static_assert(NC % 2 == 0 && (R == 68 || R == 34), "row tiles x 2 column halves + tail rows");
     constexpr int NCW = NC / 2;
     constexpr int NRW = R == 68 ? 2 : 1;            // row tiles per wave
     const int pr = gemm_pr(wave);
     const bool dup = (NCW & 1) && pr == 1;
-    gemm_wave<NRW, NCW, TM_MFMA4, 0, NC, KB, MODE, XS2, NPRE>(A, lda, Bp, NRW * pr, gemm_ch(wave) * NCW,
-                                                             col_rot<NCW>(wave), R - R % 16, dup, lane, e, pre, AX, ldx);
+    if constexpr (NSUB == 1) {
+        gemm_wave<NRW, NCW, TM_MFMA4, 0, NC, KB, MODE, XS2, NPRE>(A, lda, Bp, NRW * pr, gemm_ch(wave) * NCW,
+                                                                 col_rot<NCW>(wave), R - R % 16, dup, lane, e, pre, AX, ldx);
+    } else {
+        constexpr int N0 = NCW / 2, N1 = NCW - N0;
+        if (wave < 4)
+            gemm_wave<NRW, NCW, TM_MFMA4, 0, NC, KB, MODE, XS2, NPRE, 0, N0, N1>(
+                A, lda, Bp, NRW * pr, gemm_ch(wave) * NCW, col_rot<NCW>(wave), R - R % 16, dup, lane, e, pre, AX, ldx);
+        else
+            gemm_wave<NRW, NCW, TM_MFMA4, 0, NC, KB, MODE, XS2, NPRE, N0, N1, N1>(
+                A, lda, Bp, NRW * pr, gemm_ch(wave) * NCW, col_rot<NCW>(wave), R - R % 16, dup, lane, e, pre, AX, ldx);
+    }
 }
 
 // global column tile of local tile c of a pass starting at ctp, rotated by rot
@@ -686,6 +761,12 @@ __device__ __forceinline__ int pass_col(int ctp, int c, int rot) {
 #endif
 #ifndef DPK_PWF16
 #define DPK_PWF16 3      // f16x3 fc1: column tiles per pass (of the wave's 6)
+#endif
+#ifndef DPK_PWF16_W8
+#define DPK_PWF16_W8 6   // f16x3 fc1 on 8 waves
+#endif
+#ifndef DPK_PWQ16_W8
+#define DPK_PWQ16_W8 9   // f16x3 QKV on 8 waves: column tiles per pass (of the SIMD's 9, split between its two waves)
 #endif
 constexpr int BLKB = 1024;
 template <int G>
@@ -745,18 +826,40 @@ struct BPreH {
 template <int PW>
 __device__ __forceinline__ int passh_rot(int wave) { return gemm_pr(wave) ? (PW + 1) / 2 : 0; }
 template <int G, int NC, int KB32, int PW>
-__device__ __forceinline__ BPreH<G, PW> gemmh_prefetch(const char* Bp, int wave, int lane, int ps = 0) {
-    constexpr int BK = blkh<G>();
+__device__ __forceinline__ BPreH<G, sub_max(PW)> gemmh_prefetch(const char* Bp, int wave, int lane, int ps = 0) {
+    constexpr int BK = blkh<G>(), NP = sub_max(PW);
     const BSrcH s = bsrch<G, NC, KB32>(Bp);
     const int ctp = gemm_ch(wave) * (NC / 2) + ps * PW, rot = passh_rot<PW>(wave);
-    BPreH<G, PW> pre;
+    BPreH<G, NP> pre;
+    if constexpr (NSUB == 1) {
 #pragma unroll
-    for (int c = 0; c < PW; ++c) {
-        const int voff = lane * 16 + pass_col<PW>(ctp, c, rot) * KB32 * BK;
+        for (int c = 0; c < PW; ++c) {
+            const int voff = lane * 16 + pass_col<PW>(ctp, c, rot) * KB32 * BK;
 #pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            pre.h[k][c] = s.load(voff, k * BK);
-            if constexpr (G == 1) pre.l[k][c] = s.load(voff, k * BK + 1024);
+            for (int k = 0; k < 2; ++k) {
+                pre.h[k][c] = s.load(voff, k * BK);
+                if constexpr (G == 1) pre.l[k][c] = s.load(voff, k * BK + 1024);
+            }
+        }
+        return pre;
+    }
+    // 8 waves: the sub-wave's local tiles [c0, c0 + nown) of the pass (gemm_wave's split)
+    const int c0 = (wave >> 2) * (PW / 2), nown = wave >> 2 ? PW - PW / 2 : PW / 2;
+#pragma unroll
+    for (int c = 0; c < NP; ++c) {
+        const int voff = lane * 16 + pass_col<PW>(ctp, c0 + c, rot) * KB32 * BK;
+        if (NSUB == 1 || c < nown) {
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                pre.h[k][c] = s.load(voff, k * BK);
+                if constexpr (G == 1) pre.l[k][c] = s.load(voff, k * BK + 1024);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                pre.h[k][c] = f16x8{};
+                if constexpr (G == 1) pre.l[k][c] = f16x8{};
+            }
         }
     }
     return pre;
@@ -769,33 +872,40 @@ __device__ __forceinline__ BPreH<G, PW> gemmh_prefetch(const char* Bp, int wave,
 // other wave the rest.  XS2: the 96 columns of k-blocks 0..2 come from AX (row stride ldx) — the
 // Chebyshev GEMMs' T0 = x block where x lives (cheb_prep XSKIP).  AR: 0 A converted here; 1 converted
 // here and kept in ar[KB32][NR+1] for the later passes of the same GEMM (f16x3, K = 96); 2 taken from ar.
-template <int G, int NR, int PW, int NC, int KB32, int MODE, bool XS2, int S, int AR>
+// C0, NCS (8 waves): the wave computes the pass's local tiles [C0, C0 + NCS) and the tail tile against those of
+// them that are tail tiles (local index < ceil(PW0/2)), as gemm_wave.
+template <int G, int NR, int PW0, int NC, int KB32, int MODE, bool XS2, int S, int AR, int C0 = 0, int NCS = PW0,
+          int NPW = PW0>
 __device__ __forceinline__ void gemmh_pass(const float* A, int lda, const float* AX, int ldx, const BSrcH& src,
                                            int rt0, int ctp, int rot, int trow0, bool tail_dup, int lane,
-                                           const EpiArgs& e, const BPreH<G, PW>& pre, AFr<G> (*ar)[NR + 1]) {
+                                           const EpiArgs& e, const BPreH<G, NPW>& pre, AFr<G> (*ar)[NR + 1]) {
     constexpr int BK = blkh<G>();
-    constexpr int NQ = (PW + 1) / 2;
+    constexpr int PW = NCS;                       // the wave's own tiles: local tile C0 + c
+    constexpr int NQF = (PW0 + 1) / 2;            // tail tiles of the pass
+    constexpr int TQ = NQF - C0 < 0 ? 0 : (NQF - C0 > NCS ? NCS : NQF - C0);   // ... of this wave
+    constexpr int NQ = TQ > 0 ? TQ : 1;
+    static_assert(C0 >= 0 && NCS >= 1 && C0 + NCS <= PW0 && NPW >= NCS, "sub-wave tile range");
     // The tail rows (trow0..): a padded 16-row tile on the same 16x16x32 MFMAs as the row tiles (rows past R
     // clamped to R - 1 on load, their results discarded).  Round 6 (T16): instead of 4x4x4 MFMAs whose k-slice
     // partials were reduce-scattered over the lane rows: +3.6 % on config 3 (bf16 K=100), +1.8 % f16x3 --
     // one 16x16x32 costs 19 cycles beside the row tiles' where the two 4x4x4 it replaces cost 25
     // (profiles/r05_mfma_h_probe.txt), and the tail epilogue is the tiles' (no permlane swaps, no MFMA-result
     // pad, 16-byte stores); profiles/r06_t16_ab.txt
-    constexpr int NA = NR + 1;                  // row tiles + the tail tile
+    constexpr int NA = NR + (TQ > 0 ? 1 : 0);   // row tiles + the tail tile
     static_assert(S >= 2 && S <= KB32, "ring slots");
     lane = opaque(lane);
     const int rl = lane & 15, g = lane >> 4, kq = g * 4;
     int gcol[PW], voff[PW];
 #pragma unroll
     for (int c = 0; c < PW; ++c) {
-        gcol[c] = pass_col<PW>(ctp, c, rot);
+        gcol[c] = pass_col<PW0>(ctp, C0 + c, rot);
         voff[c] = lane * 16 + gcol[c] * KB32 * BK;
     }
     // A fragment sources: row tiles then the tail tile.  Row x stride as a 24-bit
     // multiply (v_mad_u32_u24): LLVM otherwise forms these with v_mad_u64_u32, whose undefined high
     // addend half it allocated to a register still being loaded (the epilogue constants), and the first
     // LDS read of the GEMM then waited at vmcnt(0) for the whole L2 round trip
-    int aoff[NA], xoff[NA];
+    int aoff[NR + 1], xoff[NR + 1];
 #pragma unroll
     for (int i = 0; i < NR; ++i) {
         aoff[i] = (int)__umul24((unsigned)((rt0 + i) * 16 + rl), (unsigned)lda) + kq;
@@ -804,7 +914,7 @@ __device__ __forceinline__ void gemmh_pass(const float* A, int lda, const float*
     const int trow_a = min(trow0 + rl, R - 1);
     aoff[NR] = (int)__umul24((unsigned)trow_a, (unsigned)lda) + kq;
     xoff[NR] = (int)__umul24((unsigned)trow_a, (unsigned)ldx) + kq;
-    f32x4 raw[NA][2];
+    f32x4 raw[NR + 1][2];
     auto loadA = [&](int kb) {
         if constexpr (AR != 2) {
 #pragma unroll
@@ -854,7 +964,7 @@ __device__ __forceinline__ void gemmh_pass(const float* A, int lda, const float*
     DPK_GEMM_HOOK(0);
     f32x4 acc[NR][PW], tacc[NQ];
     const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-    AFr<G> af[NA];
+    AFr<G> af[NR + 1];
     auto cvt = [&](int kb) {
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
@@ -875,7 +985,7 @@ __device__ __forceinline__ void gemmh_pass(const float* A, int lda, const float*
             for (int c = 0; c < PW; ++c) oldv[i][c] = *reinterpret_cast<const f32x4*>(rp + gcol[c] * 16);
         }
 #pragma unroll
-        for (int q = 0; q < NQ; ++q)
+        for (int q = 0; q < TQ; ++q)
             oldt[q] = *reinterpret_cast<const f32x4*>(e.dst + __umul24((unsigned)trow_a, (unsigned)e.ldd) + gcol[q] * 16 + kq);
     };
     // The epilogue is woven into the last k-block: the epilogue of the tile LAG tiles earlier rides behind
@@ -907,7 +1017,7 @@ __device__ __forceinline__ void gemmh_pass(const float* A, int lda, const float*
     };
     auto tail_mfmas = [&](int st, int kb) {
 #pragma unroll
-        for (int q = 0; q < NQ; ++q) {
+        for (int q = 0; q < TQ; ++q) {
             f32x4 t = kb == 0 ? z : tacc[q];
             const f16x8 th = af[NR].h;
             if constexpr (G == 2) {
@@ -934,7 +1044,7 @@ __device__ __forceinline__ void gemmh_pass(const float* A, int lda, const float*
         const f32x2 hi = __builtin_elementwise_fma(f32x2{a[2], a[3]}, inv2, f32x2{bias4[q][2], bias4[q][3]});
         f32x4 o = epi_value4<MODE, true>(f32x4{lo[0], lo[1], hi[0], hi[1]}, z, tp, RES ? oldt[q] : z);
         asm volatile("" : "+v"(o));   // formed on every lane: nothing sinks into the store branch
-        const bool skip = (q == NQ - 1 && tail_dup) || row >= R;
+        const bool skip = (C0 + q == NQF - 1 && tail_dup) || row >= R;
         if (!skip) *reinterpret_cast<f32x4*>(e.dst + __umul24((unsigned)row, (unsigned)e.ldd) + gcol[q] * 16 + kq) = o;
     };
 #pragma unroll
@@ -974,7 +1084,7 @@ __device__ __forceinline__ void gemmh_pass(const float* A, int lda, const float*
 #pragma unroll
     for (int tt = NR * PW > LAG ? NR * PW - LAG : 0; tt < NR * PW; ++tt) epi_tile(tt / PW, tt % PW);
 #pragma unroll
-    for (int q = 0; q < NQ; ++q) epi_tail(q);
+    for (int q = 0; q < TQ; ++q) epi_tail(q);
     DPK_GEMM_HOOK(2);
 }
 
@@ -983,7 +1093,7 @@ __device__ __forceinline__ void gemmh_pass(const float* A, int lda, const float*
 // pre: the first pass's first two B k-blocks (gemmh_prefetch).
 template <int G, int NC, int KB32, int PW, int MODE, bool XS2 = false>
 __device__ __forceinline__ void gemmh_wg(const float* A, int lda, const char* Bp, int wave, int lane, const EpiArgs& e,
-                                         const BPreH<G, PW>& pre, const float* AX = nullptr, int ldx = 0) {
+                                         const BPreH<G, sub_max(PW)>& pre, const float* AX = nullptr, int ldx = 0) {
     static_assert(NC % 2 == 0 && (NC / 2) % PW == 0 && (R == 68 || R == 34), "passes of PW column tiles");
     constexpr int NCW = NC / 2, NRW = R == 68 ? 2 : 1, NPASS = NCW / PW;
     // ring slots: 3 (all of a K = 96 GEMM's k-blocks in flight; also for the 9-tile bf16 QKV pass) unless
@@ -996,10 +1106,30 @@ __device__ __forceinline__ void gemmh_wg(const float* A, int lda, const char* Bp
     const bool dup = (PW & 1) && pr == 1;
     const BSrcH src = bsrch<G, NC, KB32>(Bp);
     const int ct0 = gemm_ch(wave) * NCW;
-    if constexpr (NPASS == 1) {
+    // the wave's local tiles [c0, c0 + ncs) of every pass (8 waves: the sub-wave's share, gemm_wave's split)
+    auto passes = [&](auto c0_, auto ncs_) {
+        constexpr int C0 = decltype(c0_)::value, NCS = decltype(ncs_)::value, NPW = sub_max(PW);
+        if constexpr (NPASS == 1) {
+            gemmh_pass<G, NRW, PW, NC, KB32, MODE, XS2, S, 0, C0, NCS, NPW>(A, lda, AX, ldx, src, NRW * pr, ct0, rot,
+                                                                            R - R % 16, dup, lane, e, pre, nullptr);
+        } else {
+            // later passes reuse the first pass's converted A fragments (K = 96: KB32 = 3)
+            AFr<G> ar[KB32][NRW + 1];
+            gemmh_pass<G, NRW, PW, NC, KB32, MODE, XS2, S, 1, C0, NCS, NPW>(A, lda, AX, ldx, src, NRW * pr, ct0, rot,
+                                                                            R - R % 16, dup, lane, e, pre, ar);
+#pragma unroll
+            for (int ps = 1; ps < NPASS; ++ps) {
+                const BPreH<G, NPW> p2 = gemmh_prefetch<G, NC, KB32, PW>(Bp, wave, lane, ps);
+                gemmh_pass<G, NRW, PW, NC, KB32, MODE, XS2, S, 2, C0, NCS, NPW>(A, lda, AX, ldx, src, NRW * pr,
+                                                                                ct0 + ps * PW, rot, R - R % 16, dup, lane,
+                                                                                e, p2, ar);
+            }
+        }
+    };
+    if constexpr (NSUB == 1 && NPASS == 1) {
         gemmh_pass<G, NRW, PW, NC, KB32, MODE, XS2, S, 0>(A, lda, AX, ldx, src, NRW * pr, ct0, rot, R - R % 16, dup,
                                                           lane, e, pre, nullptr);
-    } else {
+    } else if constexpr (NSUB == 1) {
         // later passes reuse the first pass's converted A fragments (K = 96: KB32 = 3)
         AFr<G> ar[KB32][NRW + 1];
         gemmh_pass<G, NRW, PW, NC, KB32, MODE, XS2, S, 1>(A, lda, AX, ldx, src, NRW * pr, ct0, rot, R - R % 16, dup,
@@ -1010,13 +1140,17 @@ __device__ __forceinline__ void gemmh_wg(const float* A, int lda, const char* Bp
             gemmh_pass<G, NRW, PW, NC, KB32, MODE, XS2, S, 2>(A, lda, AX, ldx, src, NRW * pr, ct0 + ps * PW, rot,
                                                               R - R % 16, dup, lane, e, p2, ar);
         }
+    } else {
+        constexpr int N0 = PW / 2;
+        if (wave < 4) passes(std::integral_constant<int, 0>{}, std::integral_constant<int, N0>{});
+        else passes(std::integral_constant<int, N0>{}, std::integral_constant<int, PW - N0>{});
     }
 }
 
 // The half-width-operand GEMM of one layer op: its first pass's B prefetch and the GEMM (gemmh_wg)
 template <int G, int NC, int KB32, int PW>
 struct HGemm {
-    using Pre = BPreH<G, PW>;
+    using Pre = BPreH<G, sub_max(PW)>;
     __device__ __forceinline__ static Pre prefetch(const char* Bp, int wave, int lane) {
         return gemmh_prefetch<G, NC, KB32, PW>(Bp, wave, lane);
     }
@@ -1114,7 +1248,7 @@ __device__ __forceinline__ void layer_norm(const float* src, float* dst, const f
     // 68 rows: 4 row tiles + one tail row per wave; 34 rows (P = 2): waves 0, 1 take row tile w
     // and tail row 32 + w, waves 2, 3 have no rows
     static_assert((RM == 64 && RT == 4) || (RM == 32 && RT == 2), "row tiles + one tail row per wave");
-    if constexpr (RM != 64)   // 34-row tiles: waves 2, 3 idle
+    if constexpr (RM != 64 || NW > 4)   // 34-row tiles: waves 2, 3 idle; 8 waves: waves 4..7
         if (w >= RT) return;
     const int row = (POSEMAP ? w * J : w * 16) + (lane >> 2), part = lane & 3;
     const int trow = POSEMAP ? w * J + 16 : RM + w;
@@ -2098,11 +2232,15 @@ __global__ void __launch_bounds__(NT, 1) sample_kernel(SampleArgs a, const float
 #else
 #define BAR() __syncthreads()
 #endif
+    // two waves per SIMD: the second (waves 4..7) at a higher static priority, so the pair does not issue
+    // in lockstep and one's MFMAs cover the other's waits
+    if constexpr (NSUB == 2)
+        if (wave >= 4) __builtin_amdgcn_s_setprio(1);
 #pragma unroll 1
     for (int s = s_beg; s < s_end; ++s) {
         // ---- gconv_input: ChebConv 5->96 (gcndiff.py:108)
         {
-            const BPre<NCD / 2> pre = gemm_prefetch<NCD, 1>(W + OFF_WIN, wave, lane);
+            const BPre<sub_max(NCD / 2)> pre = gemm_prefetch<NCD, 1>(W + OFF_WIN, wave, lane);
             input_prep<SPARSE>(CW, XST, B1, tid);
             BAR();
             const EpiArgs e{XS, LDX, W + OFF_BIN, nullptr, 0, pose0, a.N - 1};
@@ -2116,15 +2254,15 @@ __global__ void __launch_bounds__(NT, 1) sample_kernel(SampleArgs a, const float
             // half-width-operand GEMM weights of this layer (gemm modes 1, 2; offh); block set X at O16_X / GH
             constexpr int GH = G16 ? G16 : 1;              // (instantiations with G16 = 0 never read LH)
             const char* LH = arena16 + offh<GH>(l, 0);
-            constexpr int PWQ = G16 == 2 ? 9 : DPK_PWQ16;  // QKV column tiles per pass (f16x3: registers)
-            constexpr int PWF = G16 == 2 ? 6 : DPK_PWF16;  // fc1
+            constexpr int PWQ = G16 == 2 ? 9 : (NSUB == 2 ? DPK_PWQ16_W8 : DPK_PWQ16);  // QKV column tiles per pass (f16x3: registers)
+            constexpr int PWF = G16 == 2 ? 6 : (NSUB == 2 ? DPK_PWF16_W8 : DPK_PWF16);  // fc1
             constexpr int GG = G16 == 2 ? 2 : 0;           // attention's and the graph products' arithmetic
             // ---- x = x + MHA(LN0(x))   (GraAttenLayer, GraFormer.py:94-95)
             {
                 // LN0's gain/shift live in the QKV weights and bias (c = b_LN0 W + b_qkv, dpk_load_weights)
                 const EpiArgs e{B2, LD2, LW + OFF_CQKV, nullptr, 0, pose0, a.N - 1};
                 using HQ = HGemm<GH, 3 * NCD, KB32_D, PWQ>;
-                BPre<3 * NCD / 2> pre;
+                BPre<sub_max(3 * NCD / 2)> pre;
                 typename HQ::Pre preh;
                 if constexpr (G16 == 0 && !DPK_LATE(1)) pre = gemm_prefetch<3 * NCD, KB_D, DPK_QKV_NPRE>(LW + OFF_QKV, wave, lane);
                 if (DPK_RUN(8)) layer_norm<false, false>(XS, B1, LNP + l * 4 * D, LNP + l * 4 * D + D, tid);
@@ -2145,7 +2283,7 @@ __global__ void __launch_bounds__(NT, 1) sample_kernel(SampleArgs a, const float
             {
                 const EpiArgs e{XS, LDX, LW + OFF_BO, nullptr, 0, pose0, a.N - 1};
                 using HO = HGemm<GH, NCD, KB32_D, 3>;
-                BPre<NCD / 2> pre;
+                BPre<sub_max(NCD / 2)> pre;
                 typename HO::Pre preh;
                 auto o_pre = [&]() {
                     if constexpr (G16) preh = HO::prefetch(LH + O16_O / GH, wave, lane);
@@ -2173,16 +2311,18 @@ __global__ void __launch_bounds__(NT, 1) sample_kernel(SampleArgs a, const float
             gbias_load(gb, LW + OFF_BFC2, lane, wave);
             {
                 using HF = HGemm<GH, 2 * NCD, KB32_D, PWF>;
-                BPre<NCD> pre;
+                BPre<sub_max(NCD)> pre;
                 typename HF::Pre preh;
                 auto f_pre = [&]() {
                     if constexpr (G16) preh = HF::prefetch(LH + O16_FC1 / GH, wave, lane);
                     else pre = gemm_prefetch<2 * NCD, KB_D, DPK_FC1_NPRE>(LW + OFF_FC1, wave, lane);
                 };
-                constexpr bool FC1_MID = DPK_MID(4) && R == 68;   // graph1 right after LN1
+                // one wave per pose: LN1's rows of pose w are read back by the same wave's graph1, no barrier
+                constexpr bool LN1_OWN = R == 68 && NW == P;
+                constexpr bool FC1_MID = DPK_MID(4) && LN1_OWN;   // graph1 right after LN1
                 if constexpr (!DPK_LATE(4) && !FC1_MID) f_pre();
                 const GFrag gf = GG != 0 ? gfrag_load_h(LW + OFF_LG, lane) : gfrag_load(LW + OFF_LGF, lane);
-                if constexpr (R == 68) {
+                if constexpr (LN1_OWN) {
                     // LN1 rows of pose w by wave w, read back by the same wave's graph1: no barrier
                     // (LDS operations of one wave complete in order; the asm keeps the compiler's order)
                     if (DPK_RUN(8)) layer_norm<true>(XS, B1, LNP + l * 4 * D + 2 * D, LNP + l * 4 * D + 3 * D, tid);
@@ -2191,7 +2331,9 @@ __global__ void __launch_bounds__(NT, 1) sample_kernel(SampleArgs a, const float
                         if (DPK_RUN(2)) graph_mma<false, GG>(gf, B1, B1, nullptr, wave, lane, f_pre);
                     } else if (DPK_RUN(2)) graph_mma<false, GG>(gf, B1, B1, nullptr, wave, lane);
                 } else {
-                    if (DPK_RUN(8)) layer_norm(XS, B1, LNP + l * 4 * D + 2 * D, LNP + l * 4 * D + 3 * D, tid);
+                    // (8 waves: the pose-mapped rows on waves 0..3, so every row is normalised by the lanes that
+                    // normalise it on 4 waves, bitwise; graph1's two waves per pose wait at the barrier)
+                    if (DPK_RUN(8)) layer_norm<R == 68>(XS, B1, LNP + l * 4 * D + 2 * D, LNP + l * 4 * D + 3 * D, tid);
                     BAR();
                     if (DPK_RUN(2)) graph_mma<false, GG>(gf, B1, B1, nullptr, wave, lane);
                 }
@@ -2219,7 +2361,7 @@ __global__ void __launch_bounds__(NT, 1) sample_kernel(SampleArgs a, const float
                     BAR();
                     if (DPK_RUN(16 | 256)) H2::template run<E_STORE_NB>(B2, LD2, LH + O16_FC2 / GH, wave, lane, e, pre);
                 } else {
-                    const BPre<NCD / 2> pre = gemm_prefetch<NCD, KB_D2>(LW + OFF_FC2, wave, lane);
+                    const BPre<sub_max(NCD / 2)> pre = gemm_prefetch<NCD, KB_D2>(LW + OFF_FC2, wave, lane);
                     BAR();
                     if (DPK_RUN(16 | 256)) gemm_wg<NCD, KB_D2, E_STORE_NB>(B2, LD2, LW + OFF_FC2, wave, lane, e, pre);
                 }
@@ -2228,7 +2370,7 @@ __global__ void __launch_bounds__(NT, 1) sample_kernel(SampleArgs a, const float
                 const float* tp = a.tproj + (MODE == M_SAMPLE ? (size_t)s * NL * D : 0) + l * D;
                 const EpiArgs e{B1, LDX, LW + OFF_BC1, tp, EPS_MODE ? NL * D : 0, pose0, a.N - 1};
                 using HC = HGemm<GH, NCD, KB32_D3, 3>;
-                BPre<NCD / 2> pre;
+                BPre<sub_max(NCD / 2)> pre;
                 typename HC::Pre preh;
                 auto c1_pre = [&]() {
                     if constexpr (G16) preh = HC::prefetch(LH + O16_C1 / GH, wave, lane);
@@ -2255,7 +2397,7 @@ __global__ void __launch_bounds__(NT, 1) sample_kernel(SampleArgs a, const float
             {
                 const EpiArgs e{XS, LDX, LW + OFF_BC2, nullptr, 0, pose0, a.N - 1};
                 using HC = HGemm<GH, NCD, KB32_D3, 3>;
-                BPre<NCD / 2> pre;
+                BPre<sub_max(NCD / 2)> pre;
                 typename HC::Pre preh;
                 auto c2_pre = [&]() {
                     if constexpr (G16) preh = HC::prefetch(LH + O16_C2 / GH, wave, lane);

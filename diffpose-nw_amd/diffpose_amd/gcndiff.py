@@ -214,6 +214,14 @@ class _HipModel:
             raise ValueError(f"tail plan must be one of {sorted(self.TAIL_PLANS)}, got {plan!r}")
         _lib.check(self._h, "dpk_set_tail_plan", _lib.lib().dpk_set_tail_plan(self._h, self.TAIL_PLANS[plan]))
 
+    def set_tile_waves(self, waves: int = 0) -> None:
+        """Waves of the workgroup that runs a 4-pose tile of ``sample`` (see dpk_set_tile_waves): 4 (one per
+        SIMD), 8 (two per SIMD) or 0 (default: what was measured faster for the GEMM mode).  Scheduling only:
+        both instances compute bitwise the same outputs."""
+        if waves not in (0, 4, 8):
+            raise ValueError(f"tile waves must be 0, 4 or 8, got {waves!r}")
+        _lib.check(self._h, "dpk_set_tile_waves", _lib.lib().dpk_set_tile_waves(self._h, int(waves)))
+
     def debug_split(self, mode: int = 0, read: bool = False):
         """Test hook (dpk_debug_split): set the step-split handoff mode; with ``read``, wait for the
         device and return the number of second halves that recomputed their first half's steps."""

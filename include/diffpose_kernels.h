@@ -253,6 +253,17 @@ int dpk_set_gemm_mode(dpk_handle* h, int mode);
  * use plan 1 for plan 2.  The environment variable DPK_TAIL_SPLIT sets a new handle's plan. */
 int dpk_set_tail_plan(dpk_handle* h, int plan);
 
+/* Waves of the workgroup that runs a 4-pose tile of dpk_sample: 4 (one per SIMD), 8 (two per SIMD:
+ * each SIMD's GEMM column tiles split between its two waves, the per-pose phases between the two
+ * waves of a pose), or 0 (default): what the measurements chose for the handle's GEMM mode.  All
+ * 4-pose tiles of a launch, the halves of step-split tiles included, run on the same instance, so
+ * plans 0 and 2 stay bitwise equal; the 2-pose tail round, dpk_eps and dpk_pose always run 4 waves.
+ * Both instances compute bitwise the same outputs.  Handles of another model shape accept 0 and 4.  With an
+ * adjacency outside the compiled H36M pattern (the dense Chebyshev path) 0 means 4 in every mode: the dense
+ * 8-wave kernels exceed their register budget and run only when 8 is asked for.
+ * The environment variable DPK_TILE_WAVES sets a new handle's value. */
+int dpk_set_tile_waves(dpk_handle* h, int waves);
+
 /* Launch timing of the sampler kernel itself: with enable != 0, every dpk_sample /
  * dpk_eps brackets its sampler-kernel launch with a pair of HIP events on the
  * caller's stream.  dpk_profile_read waits for the recorded events and returns up to
