@@ -1280,7 +1280,10 @@ __device__ __forceinline__ void layer_norm(const float* src, float* dst, const f
     // value): S1 = sum(x - c0), S2 = sum((x - c0)^2); mean = c0 + S1/96, var = (S2 - S1^2/96)/95
     // (unbiased, GraFormer.py:64).  With the shift inside the row's range the two sums stay of the
     // order of the variance, so the one-pass form loses nothing measurable against the two-pass
-    // one, and the two reductions share one DPP chain.
+    // one, and the two reductions share one DPP chain.  Its worst case is a row whose outlier IS
+    // element 0 (S2 = 96x the variance's numerator): with gconv_input.bias[0] + 10 eps is 4.3e-6 off
+    // the fp64 oracle, against 1.3e-6 with the same outlier in channel 7, still inside the 5e-6 bar
+    // (tests/test_gpu_input_regimes.py, bias+10_ch0 / _ch7).
     f32x4 d1 = {0.f, 0.f, 0.f, 0.f}, d2 = {0.f, 0.f, 0.f, 0.f};
     const f32x2 nc0 = vpair(-c0);
 #pragma unroll

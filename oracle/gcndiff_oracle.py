@@ -42,8 +42,9 @@ H36M_EDGES = ((0, 1), (1, 2), (2, 3), (0, 4), (4, 5), (5, 6), (0, 7), (7, 8), (8
               (8, 11), (11, 12), (12, 13), (8, 14), (14, 15), (15, 16))
 
 
-def adjacency(num_pts: int = 17, edges=H36M_EDGES) -> torch.Tensor:
-    """Dense row-normalised D^-1 (A_sym + I), fp32 (GraFormer.py:32-44, sparse=False)."""
+def adjacency(num_pts: int = 17, edges=H36M_EDGES, dtype=torch.float32) -> torch.Tensor:
+    """Dense row-normalised D^-1 (A_sym + I), fp32 (GraFormer.py:32-44, sparse=False).  ``dtype``
+    casts the fp32 result (the values the kernels are given), it does not recompute it."""
     a = np.zeros((num_pts, num_pts), dtype=np.float32)
     for i, j in edges:
         a[i, j] = 1.0
@@ -52,7 +53,7 @@ def adjacency(num_pts: int = 17, edges=H36M_EDGES) -> torch.Tensor:
     rowsum = a.sum(1, dtype=np.float32)
     r_inv = np.power(rowsum, -1).astype(np.float32)
     r_inv[np.isinf(r_inv)] = 0.0
-    return torch.tensor(r_inv[:, None] * a, dtype=torch.float)
+    return torch.tensor(r_inv[:, None] * a, dtype=torch.float).to(dtype)
 
 
 def cheb_basis(graph: torch.Tensor, order: int = 3) -> torch.Tensor:
@@ -232,8 +233,11 @@ def generalized_steps(x: torch.Tensor, mask, seq, eps_fn, b: torch.Tensor, eta: 
     return xs, x0s
 
 
-def params_to_torch(sd) -> dict:
-    return {k: torch.as_tensor(np.asarray(v, dtype=np.float32)) for k, v in sd.items()}
+def params_to_torch(sd, dtype=torch.float32) -> dict:
+    """The state_dict as torch tensors: the fp32 values, held in ``dtype``.  With float64 parameters,
+    adjacency, x and betas every function above computes in float64 end to end (the float64 mode
+    of the oracle, pinned by tests/test_oracle_fp64.py)."""
+    return {k: torch.as_tensor(np.asarray(v, dtype=np.float32)).to(dtype) for k, v in sd.items()}
 
 
 def post_process(out_uvxyz: torch.Tensor, test_times: int, num_pts: int = 17) -> torch.Tensor:

@@ -147,6 +147,76 @@ def test_pose_metrics_hypotheses_and_root_quirk():
     assert e[0].shape == (0,)
 
 
+def _root(a, mode):
+    """The root handling of test_hyber on a float32 [F,17,3] array (a float32 subtraction, as the
+    reference's), then float64 for the oracle."""
+    a = a.copy()
+    if mode == "relative":
+        a = a - a[:, :1]
+    elif mode == "quirk":
+        a[:, 0] = 0.0
+    assert a.dtype == np.float32
+    return a.astype(np.float64)
+
+
+@pytest.mark.parametrize("mode", ["raw", "relative", "quirk"])
+def test_pose_metrics_degenerate_poses(mode):
+    """The alignment solver (Horn's quaternion, Jacobi sweeps capped at 16, in place of the reference's
+    SVD) on the poses where such solvers go wrong, one launch of F = 70 frames (two workgroups, the
+    second partial), frame i holding case i mod 11 of edge_inputs.METRICS_CASES: exact and
+    similarity-transformed copies (off-diagonals 0, residual 0), reflections with and without noise (the
+    sign(det R) branch), a 180 degree rotation, planar and collinear point sets (repeated / zero singular
+    values), a camera-frame offset and 1e-6-scaled poses.  Against the SVD oracle in float64 at the
+    1e-12 of test_pose_metrics_vs_golden (a numpy float64 emulation of the kernel's algorithm differs
+    from the SVD by at most 1.5e-13 on these cases); "raw" keeps the 5 m offset in the coordinates the
+    kernel centres, so there the bar is 1e-12 times the largest coordinate magnitude.  MPJPE at rtol 1e-9."""
+    from oracle import metrics_oracle as M
+    import edge_inputs as E
+
+    pred, tgt = E.metrics_edge_inputs(70)
+    out = np.zeros((70, 17, 5), np.float32)
+    out[:, :, 2:] = pred
+    p1, p2 = metrics.pose_errors(torch.from_numpy(out).cuda(), torch.from_numpy(tgt).cuda(), 1, mode)
+    p1, p2 = p1.cpu().numpy(), p2.cpu().numpy()
+    o, t = _root(pred, mode), _root(tgt, mode)
+    r1 = np.linalg.norm(o - t, axis=-1).mean(-1)
+    r2 = M.p_mpjpe_per_pose(o.copy(), t.copy())
+    assert np.isfinite(p1).all() and np.isfinite(p2).all()
+    scale = max(1.0, float(np.abs(o).max()), float(np.abs(t).max())) if mode == "raw" else 1.0
+    d = np.abs(p2 - r2)
+    case = np.arange(70) % len(E.METRICS_CASES)
+    for i, n in enumerate(E.METRICS_CASES):
+        print(f"metrics {mode} {n}: max|p2 - svd| {d[case == i].max():.3e}")
+    assert record_delta(float(d.max()), 1e-12 * scale, f"metrics/{mode}/p_mpjpe")
+    assert np.allclose(p1, r1, rtol=1e-9, atol=0)
+
+
+def test_pose_metrics_h20():
+    """H = 20 hypotheses (config 5's count) on F = 70 frames: the hypothesis mean against torch.mean at
+    1e-7 and the errors against the oracle on that mean at rtol 1e-6."""
+    from oracle import gcndiff_oracle as O
+    from oracle import metrics_oracle as M
+
+    rng = np.random.Generator(np.random.PCG64(20))
+    H, F = 20, 70
+    out = rng.normal(0, 0.3, size=(H * F, 17, 5)).astype(np.float32)
+    tgt = rng.normal(0, 0.3, size=(F, 17, 3)).astype(np.float32)
+    for mode in ("quirk", "relative"):
+        p1, p2, xyz = metrics.pose_errors(torch.from_numpy(out).cuda(), torch.from_numpy(tgt).cuda(), H, mode,
+                                          return_xyz=True)
+        o = torch.mean(torch.from_numpy(out).reshape(20, F, 17, 5), 0)[:, :, 2:]
+        t = torch.from_numpy(tgt)
+        if mode == "quirk":
+            o, t = O.root_subtract_inplace_quirk(o), O.root_subtract_inplace_quirk(t)
+        else:
+            o, t = o - o[:, :1].clone(), t - t[:, :1].clone()
+        assert float((xyz.cpu() - o).abs().max()) <= 1e-7
+        r1 = np.linalg.norm(o.double().numpy() - t.double().numpy(), axis=-1).mean(-1)
+        r2 = M.p_mpjpe_per_pose(o.double().numpy(), t.double().numpy())
+        assert np.allclose(p1.cpu().numpy(), r1, rtol=1e-6, atol=0)
+        assert np.allclose(p2.cpu().numpy(), r2, rtol=1e-6, atol=0)
+
+
 def test_runner_test_hyber_vs_oracle():
     """Diffpose.test_hyber (GCNpose -> uvxyz -> K=10 DDIM -> metrics -> per-action accounting)
     against the same pipeline built from the oracle, on two synthetic batches."""
