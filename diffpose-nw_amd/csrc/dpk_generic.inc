@@ -1,9 +1,10 @@
-// dpk_generic.inc — the GCNdiff / GCNpose forward for model shapes other than the compiled one.
+// dpk_generic.inc — the GCNdiff / GCNpose forward for model shapes no sampler instance is compiled for.
 //
 // The persistent sampler (dpk_sampler.inc) is built for the shape every reference config uses
-// (configs/human36m_*.yml:9-16: hid_dim 96, n_head 4, n_pts 17, coords [5,5] / [2,3]).  A config
-// with another hid_dim, n_head or n_pts (models/gcndiff.py:55-99 builds GCNdiff from any of them)
-// runs here instead: the same layer sequence as plain HIP kernels over activations in HBM, one
+// (configs/human36m_*.yml:9-16: hid_dim 96, n_head 4, n_pts 17, coords [5,5] / [2,3]) and for GCNdiff at four
+// other widths (dpk_kernels.hip: INSTANCES).  A config with any other hid_dim, n_head or n_pts
+// (models/gcndiff.py:55-99 builds GCNdiff from any of them), and every handle made under DPK_FORCE_GENERIC=1
+// or (the other widths) DPK_GEN_FUSED=0, gets a GenModel and runs here instead: the same layer sequence as plain HIP kernels over activations in HBM, one
 // launch per op, fp32 throughout (the reference's order of operations per op; GEMM sums on the fp32 MFMA):
 //   ChebConv   cheb_basis [X | T1 X | T2 X] -> gemm (ChebConv.py:74-88, stacked K = 3*in); every gemm on
 //              the fp32 matrix cores (v_mfma_f32_16x16x4_f32)
@@ -640,22 +641,8 @@ struct GenPack {
     size_t w, off;
     int K, N, NJ;
 };
-// The persistent sampler compiled at other model widths (round 5): GCNdiff at hid 128 / 8 heads (namespace
-// dpkw, 2-pose tiles), hid 128 / 4 heads (dpkw4), hid 64 / 2 heads (dpkn, 4-pose tiles) or hid 64 / 4 heads
-// (dpkn4), 17 joints, num_layer <= 5, coords 5 -> 5,
-// fp32 GEMMs, runs that instance's sample_kernel — the same fused K-step loop as the shipped shape —
-// instead of the per-op launches below; its arena is packed on the host from the staging by the instance's
-// pack_model (dpk_pack.inc).  DPK_GEN_FUSED=0 keeps such a handle on the per-op path (A/B; tests compare the two).
-struct GenFused {
-    int inst = 0;                // index into the instance list below (gen_new: the first that fits)
-    Packed pk;                   // the instance's arenas (its pack_model), no half-width copies
-    float* arena = nullptr;
-    float* temb = nullptr;
-};
-
 struct GenModel {
-    Stage s;                   // host staging of the weights and the graph; `dev` is its device copy
-    GenFused* fz = nullptr;    // non-null: the fused wide-model sampler serves dpk_sample / dpk_eps
+    const Stage& s;            // the handle's host staging of the weights and the graph; `dev` is its device copy
     std::vector<GenPack> packs;
     std::vector<float> hp;     // host staging of the packed arena
     float* devp = nullptr;     // device packed arena
@@ -677,49 +664,7 @@ static void gen_drop_graphs(GenModel* g, const float* scratch) {   // scratch nu
 // had none yet): the loops recorded over it go first
 static void gen_scratch_replaced(void* g, const float* old) { gen_drop_graphs(static_cast<GenModel*>(g), old); }
 
-// the instance serving a GenFused handle (GenFused::inst): 0 dpkw, 1 dpkw4, 2 dpkn, 3 dpkn4
-#define DPK_FZ_SWITCH(INST, CALL)          \
-    switch (INST) {                        \
-        case 0: dpkw::CALL; break;         \
-        case 1: dpkw4::CALL; break;        \
-        case 2: dpkn::CALL; break;         \
-        default: dpkn4::CALL; break;       \
-    }
-static int gen_fused_pick(int D, int H, int J, int L, int cin, int cout, int kind) {
-    if (dpkw::fused_fits(D, H, J, L, cin, cout, kind)) return 0;
-    if (dpkw4::fused_fits(D, H, J, L, cin, cout, kind)) return 1;
-    if (dpkn::fused_fits(D, H, J, L, cin, cout, kind)) return 2;
-    if (dpkn4::fused_fits(D, H, J, L, cin, cout, kind)) return 3;
-    return -1;
-}
-static void gen_fused_pack(GenModel* g) { DPK_FZ_SWITCH(g->fz->inst, pack_model(g->s, g->fz->pk, false)) }
-template <int MODE>
-static void gen_fused_launch(GenModel* g, const SampleArgs& a, hipStream_t st) {
-    DPK_FZ_SWITCH(g->fz->inst, template fused_launch<MODE>(g->fz->pk.sparse, g->fz->arena, a, st))
-}
-static void gen_fused_temb(const GenFused* f, const float* t, int stride, int count, float* out, hipStream_t st) {
-    DPK_FZ_SWITCH(f->inst, fused_temb(f->temb, t, stride, count, out, st))
-}
-static size_t gen_fused_tp(const GenFused* f) {
-    switch (f->inst) {
-        case 0: return dpkw::FUSED_TP;
-        case 1: return dpkw4::FUSED_TP;
-        case 2: return dpkn::FUSED_TP;
-        default: return dpkn4::FUSED_TP;
-    }
-}
-
-static GenModel* gen_new(int D, int H, int J, int L, int cin, int cout, int kind) {
-    GenModel* g = new GenModel();
-    stage_init(g->s, D, H, J, L, cin, cout, kind);
-    const char* fe = getenv("DPK_GEN_FUSED");
-    const int inst = (fe && atoi(fe) == 0) ? -1 : gen_fused_pick(D, H, J, L, cin, cout, kind);
-    if (inst >= 0) {
-        g->fz = new GenFused();
-        g->fz->inst = inst;
-    }
-    return g;
-}
+static GenModel* gen_new(const Stage& s) { return new GenModel{s}; }
 
 static int gen_graph_count(const GenModel* g) { return g ? (int)g->graphs.size() : 0; }
 
@@ -727,11 +672,6 @@ static void gen_free(GenModel* g) {
     if (!g) return;
     (void)hipDeviceSynchronize();
     gen_drop_graphs(g, nullptr);
-    if (g->fz) {
-        if (g->fz->arena) (void)hipFree(g->fz->arena);
-        if (g->fz->temb) (void)hipFree(g->fz->temb);
-        delete g->fz;
-    }
     if (g->dev) (void)hipFree(g->dev);
     if (g->devp) (void)hipFree(g->devp);
     delete g;
@@ -772,14 +712,6 @@ static void gen_pack(GenModel* g) {
 static int gen_upload(dpk_handle* h, GenModel* g) {
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipDeviceSynchronize());   // launches in flight may read the arena
-    if (g->fz) {
-        gen_fused_pack(g);
-        GenFused* f = g->fz;
-        if (!f->arena) HIPCHK(h, hipMalloc(&f->arena, f->pk.arena.size() * 4));
-        if (!f->temb) HIPCHK(h, hipMalloc(&f->temb, f->pk.temb.size() * 4));
-        HIPCHK(h, hipMemcpy(f->arena, f->pk.arena.data(), f->pk.arena.size() * 4, hipMemcpyHostToDevice));
-        HIPCHK(h, hipMemcpy(f->temb, f->pk.temb.data(), f->pk.temb.size() * 4, hipMemcpyHostToDevice));
-    }
     if (!g->dev) HIPCHK(h, hipMalloc(&g->dev, g->s.floats * 4));
     HIPCHK(h, hipMemcpy(g->dev, g->s.h.data(), g->s.floats * 4, hipMemcpyHostToDevice));
     gen_pack(g);
@@ -788,8 +720,9 @@ static int gen_upload(dpk_handle* h, GenModel* g) {
     return DPK_OK;
 }
 
-// n floats of scratch for a generic call (call_scratch), a captured call's refusals in floats.  The pool costs
-// one more scratch-sized buffer per generic handle, its spare.
+// n floats of scratch for a call off the shipped shape (call_scratch; per-op handles, and the timestep
+// projections of the other widths' instances), a captured call's refusals in floats.  The pool costs one more
+// scratch-sized buffer per such handle, its spare.
 static int gen_scratch(dpk_handle* h, hipStream_t st, bool cap, size_t n, float** out, const char* who) {
     ScratchBuf buf;
     ScratchStatus why;
@@ -944,44 +877,12 @@ static void gen_temb(GenModel* g, hipStream_t st, const float* tvals, int tstrid
                        W + g->s.d1b, W + g->s.wtp, W + g->s.btp, tvals, tstride, g->s.D, g->s.E, g->s.L, neg, tproj);
 }
 
-// dpk_sample / dpk_eps on a GenFused handle: scratch for the timestep projections ([K][NL][D] of the schedule,
-// per call; [N][NL][D] per pose), the projections, one launch of the instance's sampler
-template <int MODE>
-static int gen_fused_run(dpk_handle* h, const SampleArgs& a, hipStream_t st, bool cap, const char* who) {
-    return profiled(h, st, cap, who, [&]() -> int {
-        gen_fused_launch<MODE>(h->gen, a, st);
-        HIPCHK(h, hipGetLastError());
-        return DPK_OK;
-    });
-}
-static int gen_fused_sample(dpk_handle* h, Sched* sc, const float* x, float* out, float* xs, float* x0s, int N,
-                            uint64_t seed, const float* noise, hipStream_t st, bool cap) {
-    const GenModel* g = h->gen;
-    float* S = nullptr;
-    int rc = gen_scratch(h, st, cap, (size_t)sc->K * gen_fused_tp(g->fz), &S, "dpk_sample");
-    if (rc) return rc;
-    gen_fused_temb(g->fz, sc->coef + 5, 6, sc->K, S, st);
-    if (xs) HIPCHK(h, hipMemcpyAsync(xs, x, (size_t)N * g->s.J * g->s.cin * 4, hipMemcpyDeviceToDevice, st));
-    rc = gen_fused_run<M_SAMPLE>(h, sample_args(h, g->fz->arena, S, sc, x, out, xs, x0s, N, seed, noise), st, cap,
-                                 "dpk_sample");
-    return rc ? rc : sched_note_use(h, sc, st, cap);
-}
-static int gen_fused_eps(dpk_handle* h, const float* x, const float* t, float* eps, int N, hipStream_t st, bool cap) {
-    const GenFused* f = h->gen->fz;
-    float* S = nullptr;
-    const int rc = gen_scratch(h, st, cap, (size_t)N * gen_fused_tp(f), &S, "dpk_eps");
-    if (rc) return rc;
-    gen_fused_temb(f, t, 1, N, S, st);
-    return gen_fused_run<M_EPS>(h, eps_args(h, f->arena, S, x, eps, N), st, cap, "dpk_eps");
-}
-
 // dpk_sample on the generic path: one forward + DDIM update per step.  Without trajectory outputs or
 // caller noise the loop is the recorded hipGraph over the state buffer xt in the scratch (x copied in,
 // the final copied out); otherwise the launches go straight to the caller's stream, the state in `out`.
 // DPK_GEN_GRAPH=0 turns the graph off (A/B).
 static int gen_sample(dpk_handle* h, Sched* sc, const float* x, float* out, float* xs, float* x0s, int N,
                       uint64_t seed, const float* noise, hipStream_t st, bool cap) {
-    if (h->gen->fz) return gen_fused_sample(h, sc, x, out, xs, x0s, N, seed, noise, st, cap);
     GenModel* g = h->gen;
     const int K = sc->K;
     const long long n = (long long)N * g->s.J * g->s.cin;
@@ -1065,7 +966,6 @@ static int gen_sample(dpk_handle* h, Sched* sc, const float* x, float* out, floa
 
 // dpk_eps on the generic path: per-pose timestep projections, one forward
 static int gen_eps(dpk_handle* h, const float* x, const float* t, float* eps, int N, hipStream_t st, bool cap) {
-    if (h->gen->fz) return gen_fused_eps(h, x, t, eps, N, st, cap);
     GenModel* g = h->gen;
     const size_t act = gen_act_floats(g, N);
     float* S = nullptr;

@@ -1,15 +1,18 @@
 // The persistent sampler's host side for one instance: included by dpk_kernels.hip inside every instance
-// namespace right after dpk_sampler.inc (dpk / dpk2: the shipped shape's 4- and 2-pose tiles; dpkw / dpkw4:
-// hid 128 with 8 / 4 heads, 2-pose tiles; dpkn / dpkn4: hid 64 with 2 / 4 heads, 4-pose tiles), so every
-// unqualified shape constant below is that instance's.  The shipped path (launch_tiles) and the generic
-// path (GenFused, for a handle whose shape an instance was compiled for) call these.
+// namespace right after dpk_sampler.inc (dpk / dpk8 / dpk2: the shipped shape's 4-pose tile on 4 and 8 waves
+// and its 2-pose tile; dpkw / dpkw4: hid 128 with 8 / 4 heads, 2-pose tiles; dpkn / dpkn4: hid 64 with 2 / 4
+// heads, 4-pose tiles), so every unqualified shape constant below is that instance's.  What the host knows an
+// instance by (SamplerInst, dpk_kernels.hip: INSTANCES) is made of SHAPE (plain C++: a CPU-only build that
+// includes this file after dpk_layout.inc compiles it too, tests/c/dpk_pack_check.cpp) and, in HIP builds,
+// fused_temb and launch_sample; which kernel modes exist for which instance is decided beside the table.
 #include "dpk_pack.inc"
 
-static bool fused_fits(int Dm, int Hm, int Jm, int Lm, int cin, int cout, int kind) {
-    return Dm == D && Hm == NH && Jm == J && Lm <= NL && kind == 0 && cin == CIN && cout == COUT;
-}
-constexpr size_t FUSED_TP = (size_t)NL * D;     // timestep projections per step (sample) or pose (eps)
+// the GCNpose kernels (coords 2 -> 3) are compiled for the shipped shape's 4-wave tiles alone
+constexpr InstShape SHAPE = {D, NH, J, NL, P, NW, NT, SM_FLOATS * 4, (size_t)NL * D, HALF_MODES, HALF_MODES && NW == 4,
+                             CIN, COUT, ARENA_FLOATS, TEMB_FLOATS, HALF_MODES ? ARENA16_BYTES : 0,
+                             HALF_MODES ? ARENA16_BYTES / 2 : 0, pack_model};
 
+#ifdef __HIPCC__
 static void fused_temb(const float* temb, const float* t, int stride, int count, float* out, hipStream_t st) {
     hipLaunchKernelGGL(temb_kernel, dim3((unsigned)count), dim3(256), 0, st, temb, t, stride, out);
 }
@@ -46,9 +49,4 @@ static void launch_sample(bool sparse, int gm, int blocks, size_t shmem, hipStre
     if (sparse) launch_gemm_mode<MODE, true, 0>(gm, grid, shmem, st, a, W, W16);
     else launch_gemm_mode<MODE, false, 0>(gm, grid, shmem, st, a, W, W16);
 }
-
-// ceil(N / P) tiles (P = 2 at hid 128, 4 at hid 64), fp32 GEMMs
-template <int MODE>
-static void fused_launch(bool sparse, const float* arena, const SampleArgs& a, hipStream_t st) {
-    launch_sample<MODE>(sparse, 0, (a.N + P - 1) / P, 0, st, a, arena, nullptr);
-}
+#endif

@@ -112,6 +112,20 @@ struct SampleArgs {
 #include "dpk_stage.inc"
 #include "dpk_scratch.inc"
 
+// All the host knows a compiled sampler instance by: its shape half (dpk_stage.inc) and how to launch it.  One
+// per instance namespace, built where the table is (INSTANCES).
+struct SamplerInst : InstShape {
+    using Launch = void (*)(bool sparse, int gm, int blocks, size_t shmem, hipStream_t st,
+                            const dpk_shared::SampleArgs& a, const float* W, const char* W16);
+    void (*temb)(const float* temb, const float* t, int stride, int count, float* out, hipStream_t st);
+    Launch launch[3];            // per kernel mode (M_SAMPLE, M_EPS, M_POSE); null: not compiled
+    const SamplerInst* wave8;    // the same tile on 8 waves (M_SAMPLE only), or null
+    const SamplerInst* tail2;    // the 2-pose tile of the same shape (launch_sampler's tail plans), or null
+    // dpk_sample's timestep projections: true, the schedule's (Sched::tps, built per schedule and weight upload);
+    // false, computed by every call into K * tp floats of pool scratch (then counted in floats, eps_scratch)
+    bool sched_tps;
+};
+
 #define DPK_P 4
 namespace dpk {
 #include "dpk_sampler.inc"
@@ -133,8 +147,8 @@ namespace dpk2 {
 #include "dpk_genfused.inc"
 }  // namespace dpk2
 // The persistent sampler at a wider model (round 5): hid 128 / 8 heads (d_k 16), 2-pose tiles (4-pose
-// tiles of 128-wide rows do not fit 160 KB of LDS), fp32 GEMMs; run by the generic-shape path for that
-// shape instead of its per-op launches (dpk_generic.inc, GenFused)
+// tiles of 128-wide rows do not fit 160 KB of LDS), fp32 GEMMs; a handle of that shape runs it instead of the
+// per-op launches of dpk_generic.inc
 #undef DPK_P
 #define DPK_P 2
 #undef DPK_D
@@ -244,10 +258,20 @@ static void cap_release_cb(void* p) {
     if (c->refs.fetch_sub(1) == 1) delete c;
 }
 
-struct GenModel;   // dpk_generic.inc: the forward for model shapes other than the compiled one
+// The weights of a handle that runs a sampler instance, as that instance reads them
+struct InstWeights {
+    const SamplerInst* inst = nullptr;   // null: a per-op handle (dpk_handle::gen)
+    Packed pk;                     // the arenas packed from the handle's staging (inst->pack), as uploaded
+    float* arena = nullptr;        // device: packed weights + graph constants
+    float* temb = nullptr;         // device: timestep-MLP weights
+    char* arena16 = nullptr;       // device: split-fp16 GEMM weights (gemm mode 1; instances with half_modes)
+    char* arenabf = nullptr;       // device: bf16 GEMM weights (gemm mode 2), same layout
+};
+
+struct GenModel;   // dpk_generic.inc: the per-op forward for model shapes no instance is compiled for
 struct dpk_handle {
     int device = 0;
-    GenModel* gen = nullptr;       // non-null: this handle's shape runs on the generic path
+    GenModel* gen = nullptr;       // non-null: this handle's shape runs on the per-op path (then w.inst is null)
     int n_pts = J;                 // joints of the handle's model
     int kind = 0;                  // 0: GCNdiff (coords 5->5), 1: GCNpose (coords 2->3)
     int num_layers = NL;           // config num_layer (1..NL): layers the kernels run
@@ -262,18 +286,14 @@ struct dpk_handle {
     unsigned token = 0;            // per-launch handoff token (30 bits, never 0)
     std::vector<CapRes*> caps;     // resources of captured launches (per capture)
     std::string err;
-    float* arena = nullptr;        // device: packed weights + graph constants
-    float* temb = nullptr;         // device: timestep-MLP weights
+    InstWeights w;                 // the sampler instance serving this handle and its weights
     float* tproj_zero = nullptr;   // device: [NL][D] zeros (GCNpose: no timestep projection)
     hipStream_t aux = nullptr;     // handle-internal stream for schedule construction
     uint64_t weights_gen = 0;      // bumped by every weight/graph upload
     Sched* sched = nullptr;        // current schedule
     std::vector<Sched*> retired;   // replaced schedules not yet known to be unused
-    ScratchPool pool;              // dpk_eps's projections [N][NL][D] (shipped shape) or the generic path's scratch
-    Stage stage;                   // host staging of the weights and the graph (the shipped shape; else gen's)
-    Packed pk;                     // the arenas packed from it (dpk::pack_model), as uploaded
-    char* arena16 = nullptr;       // device: split-fp16 GEMM weights (gemm mode 1)
-    char* arenabf = nullptr;       // device: bf16 GEMM weights (gemm mode 2), same layout
+    ScratchPool pool;              // timestep projections of dpk_eps (and dpk_sample, !sched_tps) or per-op scratch
+    Stage stage;                   // host staging of the weights and the graph, whatever the shape
     int gemm_mode = 0;             // 0: fp32 MFMA, 1: 3x fp16-split MFMA, 2: bf16 MFMA (dpk_set_gemm_mode)
     int tile_waves = 0;            // dpk_set_tile_waves: 4 or 8 waves on the 4-pose tiles of dpk_sample; 0 the mode's default
     bool have_graph = false, have_weights = false;
@@ -450,13 +470,17 @@ static int sched_note_use(dpk_handle* h, Sched* s, hipStream_t st, bool cap) {
 
 // tps of `s` from the current weights, on the handle's own stream; returns once they are written
 static int sched_compute_tps(dpk_handle* h, Sched* s) {
-    hipLaunchKernelGGL(temb_kernel, dim3(s->K), dim3(256), 0, h->aux, h->temb, s->coef + 5, 6, s->tps);
+    h->w.inst->temb(h->w.temb, s->coef + 5, 6, s->K, s->tps, h->aux);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->aux));
     s->tps_gen = h->weights_gen;
     return DPK_OK;
 }
 
+// Does the handle's instance read dpk_sample's timestep projections from the schedule (SamplerInst::sched_tps)?
+static bool sched_tps(const dpk_handle* h) { return h->w.inst && h->w.inst->sched_tps; }
+
+// The arenas packed for the handle's instance (h->w.pk), to the device
 static int upload(dpk_handle* h) {
     HIPCHK(h, hipSetDevice(h->device));
     // launches already enqueued on any stream may still read the arena: overwrite it only after
@@ -465,16 +489,19 @@ static int upload(dpk_handle* h) {
     // every uncaptured launch has completed: the retired schedules only they used go now, so the
     // projections below are recomputed for the current schedule and the graph-pinned ones only
     sched_sweep(h);
-    if (!h->arena) HIPCHK(h, hipMalloc(&h->arena, (size_t)ARENA_FLOATS * 4));
-    if (!h->arena16) HIPCHK(h, hipMalloc(&h->arena16, (size_t)ARENA16_BYTES));
-    HIPCHK(h, hipMemcpy(h->arena16, h->pk.a16.data(), (size_t)ARENA16_BYTES, hipMemcpyHostToDevice));
-    if (!h->arenabf) HIPCHK(h, hipMalloc(&h->arenabf, (size_t)ARENAB_BYTES));
-    HIPCHK(h, hipMemcpy(h->arenabf, h->pk.abf.data(), (size_t)ARENAB_BYTES, hipMemcpyHostToDevice));
-    if (!h->temb) HIPCHK(h, hipMalloc(&h->temb, (size_t)TEMB_FLOATS * 4));
-    HIPCHK(h, hipMemcpy(h->arena, h->pk.arena.data(), (size_t)ARENA_FLOATS * 4, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(h->temb, h->pk.temb.data(), (size_t)TEMB_FLOATS * 4, hipMemcpyHostToDevice));
+    InstWeights& w = h->w;
+    if (!w.arena) HIPCHK(h, hipMalloc(&w.arena, w.inst->arena_floats * 4));
+    if (!w.temb) HIPCHK(h, hipMalloc(&w.temb, w.inst->temb_floats * 4));
+    HIPCHK(h, hipMemcpy(w.arena, w.pk.arena.data(), w.inst->arena_floats * 4, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(w.temb, w.pk.temb.data(), w.inst->temb_floats * 4, hipMemcpyHostToDevice));
+    if (w.inst->half_modes) {
+        if (!w.arena16) HIPCHK(h, hipMalloc(&w.arena16, w.inst->arena16_bytes));
+        HIPCHK(h, hipMemcpy(w.arena16, w.pk.a16.data(), w.inst->arena16_bytes, hipMemcpyHostToDevice));
+        if (!w.arenabf) HIPCHK(h, hipMalloc(&w.arenabf, w.inst->arenabf_bytes));
+        HIPCHK(h, hipMemcpy(w.arenabf, w.pk.abf.data(), w.inst->arenabf_bytes, hipMemcpyHostToDevice));
+    }
     ++h->weights_gen;
-    if (!h->have_weights || h->kind != 0) return DPK_OK;
+    if (!h->have_weights || h->kind != 0 || !sched_tps(h)) return DPK_OK;
     // every live schedule (current, retired, pinned by a graph) follows the new weights
     if (h->sched) {
         const int rc = sched_compute_tps(h, h->sched);
@@ -548,27 +575,15 @@ constexpr int TILE_WAVES_DEFAULT[3] = {8, 4, 8};   // fp32, f16x3, bf16
 // dense kernels already fill 512) and were not measured; they run on explicit request only.
 static int tile_waves(const dpk_handle* h) {
     if (h->tile_waves) return h->tile_waves;
-    return h->pk.sparse ? TILE_WAVES_DEFAULT[h->gemm_mode] : 4;
+    return h->w.pk.sparse ? TILE_WAVES_DEFAULT[h->gemm_mode] : 4;
 }
 
-// One launch of the sampler kernel with tile size PT (4: dpk, 2: dpk2) for the handle's graph
-// pattern and GEMM mode.
-template <int MODE, int PT>
-static void launch_tiles(dpk_handle* h, int blocks, size_t shmem, hipStream_t st, const SampleArgs& a) {
-    const char* a16 = h->gemm_mode == 2 ? h->arenabf : h->arena16;
-    if constexpr (PT == 4) {
-        // every 4-pose tile of a dpk_sample launch, step-split halves included, on one instance; dpk_eps and
-        // dpk_pose stay on 4 waves
-        if constexpr (MODE == M_SAMPLE) {
-            if (tile_waves(h) == 8) {
-                dpk8::launch_sample<MODE>(h->pk.sparse, h->gemm_mode, blocks, shmem, st, a, h->arena, a16);
-                return;
-            }
-        }
-        dpk::launch_sample<MODE>(h->pk.sparse, h->gemm_mode, blocks, shmem, st, a, h->arena, a16);
-    } else {
-        dpk2::launch_sample<MODE>(h->pk.sparse, h->gemm_mode, blocks, shmem, st, a, h->arena, a16);
-    }
+// One launch of kernel mode `mode` on the instance `tile` (the handle's, or a sibling tile of it) for the
+// handle's graph pattern and GEMM mode.
+static void launch_tiles(dpk_handle* h, const SamplerInst* tile, int mode, int blocks, size_t shmem, hipStream_t st,
+                         const SampleArgs& a) {
+    const char* a16 = h->gemm_mode == 2 ? h->w.arenabf : h->w.arena16;
+    tile->launch[mode](h->w.pk.sparse, h->gemm_mode, blocks, shmem, st, a, h->w.arena, a16);
 }
 
 // The sampler over a.N poses.  One 4-pose workgroup per CU per round; a partial last round of r
@@ -584,11 +599,21 @@ static void launch_tiles(dpk_handle* h, int blocks, size_t shmem, hipStream_t st
 // CUs idle (at most 2 poses per CU remain) those poses run as 2-pose workgroups (dpk2, about 0.6
 // of a 4-pose tile's time), one per CU, in a second launch after the full rounds.  Each
 // workgroup's result depends only on its own poses.
-template <int MODE>
-static int launch_sampler(dpk_handle* h, hipStream_t st, SampleArgs a, bool cap) {
-    const int N = a.N;
+// Both plans need the 2-pose sibling (plan 2 falls back on plan 1): an instance without one (the other
+// widths) runs ceil(N / P) of its tiles in one launch.
+static int launch_sampler(dpk_handle* h, int mode, hipStream_t st, SampleArgs a, bool cap) {
+    const SamplerInst* in = h->w.inst;
+    const int N = a.N, P = in->P;
+    if (!in->tail2) {
+        launch_tiles(h, in, mode, (N + P - 1) / P, 0, st, a);
+        HIPCHK(h, hipGetLastError());
+        return DPK_OK;
+    }
+    // every 4-pose tile of a dpk_sample launch, step-split halves included, on one instance; dpk_eps and
+    // dpk_pose stay on 4 waves
+    const SamplerInst* tile = mode == M_SAMPLE && in->wave8 && tile_waves(h) == 8 ? in->wave8 : in;
     const int round4 = P * h->n_cu;
-    if constexpr (MODE == M_SAMPLE) {
+    if (mode == M_SAMPLE) {
         const int tiles = (N + P - 1) / P, q = tiles / h->n_cu, r = tiles % h->n_cu;
         if (h->tail_plan == 2 && a.K >= 2 && q >= 1 && r > 0 && 2 * r <= h->n_cu) {
             const int slot = split_slot(h, st, cap);
@@ -603,7 +628,7 @@ static int launch_sampler(dpk_handle* h, hipStream_t st, SampleArgs a, bool cap)
                 h->token = (h->token + 1) & 0x3fffffffu;
                 if (h->token == 0) h->token = 1;
                 a.token = h->token;
-                launch_tiles<MODE, P>(h, q * h->n_cu + 2 * r, 0, st, a);
+                launch_tiles(h, tile, mode, q * h->n_cu + 2 * r, 0, st, a);
                 HIPCHK(h, hipGetLastError());
                 return cap ? DPK_OK : split_slot_hold(h, slot, st);
             }
@@ -614,15 +639,15 @@ static int launch_sampler(dpk_handle* h, hipStream_t st, SampleArgs a, bool cap)
     if (h->tail_plan >= 1 && rem != 0 && rem <= 2 * h->n_cu) n4 = N - rem;
     if (n4 > 0) {
         a.pose_off = 0;
-        launch_tiles<MODE, P>(h, (n4 + P - 1) / P, 0, st, a);
+        launch_tiles(h, tile, mode, (n4 + P - 1) / P, 0, st, a);
     }
     if (n4 < N) {
         // pad the 2-pose kernel's LDS past half a CU's so the dispatcher places one per CU
-        constexpr int P2 = dpk2::P;
-        constexpr size_t half = 160 * 1024 / 2, lds2 = (size_t)dpk2::SM_FLOATS * 4;
-        constexpr size_t pad = lds2 > half ? 0 : half - lds2 + 256;
+        const int P2 = in->tail2->P;
+        const size_t half = 160 * 1024 / 2, lds2 = (size_t)in->tail2->lds_bytes;
+        const size_t pad = lds2 > half ? 0 : half - lds2 + 256;
         a.pose_off = n4;
-        launch_tiles<MODE, P2>(h, (N - n4 + P2 - 1) / P2, pad, st, a);
+        launch_tiles(h, in->tail2, mode, (N - n4 + P2 - 1) / P2, pad, st, a);
     }
     HIPCHK(h, hipGetLastError());
     return DPK_OK;
@@ -649,7 +674,7 @@ static int call_scratch(dpk_handle* h, hipStream_t st, bool cap, size_t n, const
 }
 
 // Launch arguments of one eps / sample / pose call over N poses, for whichever sampler instance `arena` was
-// packed for (the shipped shape's, or a GenFused handle's): tproj per pose, per step of `sc`, or zeros.
+// packed for: tproj per pose, per step of `sc`, or zeros.
 static SampleArgs eps_args(const dpk_handle* h, const float* arena, const float* tproj, const float* x, float* out,
                            int N) {
     SampleArgs a{};
@@ -688,6 +713,68 @@ static SampleArgs pose_args(const dpk_handle* h, const float* arena, const float
 
 #include "dpk_generic.inc"
 
+// ---------------------------------------------------------------------------------------
+// The compiled sampler instances: which shapes have a fused kernel, on which tile, with which kernel modes.
+// First the launchers that exist, instantiated explicitly: these and no others (a mode not listed for an
+// instance is a null pointer in its descriptor below; naming it there would compile kernels nobody runs).
+// The kernels stand in the code object in this list's order, however the host code is arranged.
+#define DPK_LAUNCHER(ns, MODE)                                                                                  \
+    template void ns::launch_sample<MODE>(bool, int, int, size_t, hipStream_t, const SampleArgs&, const float*, \
+                                          const char*);
+DPK_LAUNCHER(dpkw, M_SAMPLE) DPK_LAUNCHER(dpkw4, M_SAMPLE) DPK_LAUNCHER(dpkn, M_SAMPLE) DPK_LAUNCHER(dpkn4, M_SAMPLE)
+DPK_LAUNCHER(dpkw, M_EPS) DPK_LAUNCHER(dpkw4, M_EPS) DPK_LAUNCHER(dpkn, M_EPS) DPK_LAUNCHER(dpkn4, M_EPS)
+DPK_LAUNCHER(dpk, M_EPS) DPK_LAUNCHER(dpk2, M_EPS)
+DPK_LAUNCHER(dpk8, M_SAMPLE) DPK_LAUNCHER(dpk, M_SAMPLE) DPK_LAUNCHER(dpk2, M_SAMPLE)
+DPK_LAUNCHER(dpk, M_POSE) DPK_LAUNCHER(dpk2, M_POSE)
+#undef DPK_LAUNCHER
+
+// The descriptors: {shape half, timestep MLP, {M_SAMPLE, M_EPS, M_POSE}, 8-wave sibling, 2-pose sibling, sched_tps}
+#define DPK_INST(ns, ...) \
+    namespace ns { constexpr SamplerInst INST = {SHAPE, fused_temb, __VA_ARGS__}; }
+// the shipped shape (hid 96 / 4 heads): its 8-wave and 2-pose tiles are reached through the 4-pose tile's entry
+DPK_INST(dpk8, {launch_sample<M_SAMPLE>, nullptr, nullptr}, nullptr, nullptr, true)
+DPK_INST(dpk2, {launch_sample<M_SAMPLE>, launch_sample<M_EPS>, launch_sample<M_POSE>}, nullptr, nullptr, true)
+DPK_INST(dpk, {launch_sample<M_SAMPLE>, launch_sample<M_EPS>, launch_sample<M_POSE>}, &dpk8::INST, &dpk2::INST, true)
+// hid 128 / 8 and 4 heads (2-pose tiles), hid 64 / 2 and 4 heads (4-pose tiles): GCNdiff, fp32 GEMMs
+DPK_INST(dpkw, {launch_sample<M_SAMPLE>, launch_sample<M_EPS>, nullptr}, nullptr, nullptr, false)
+DPK_INST(dpkw4, {launch_sample<M_SAMPLE>, launch_sample<M_EPS>, nullptr}, nullptr, nullptr, false)
+DPK_INST(dpkn, {launch_sample<M_SAMPLE>, launch_sample<M_EPS>, nullptr}, nullptr, nullptr, false)
+DPK_INST(dpkn4, {launch_sample<M_SAMPLE>, launch_sample<M_EPS>, nullptr}, nullptr, nullptr, false)
+#undef DPK_INST
+
+// dpk_create gives a handle the first entry that fits its config; a config none fits runs per op (GenModel)
+constexpr const SamplerInst* INSTANCES[] = {&dpk::INST, &dpkw::INST, &dpkw4::INST, &dpkn::INST, &dpkn4::INST};
+constexpr bool instances_consistent() {
+    for (const SamplerInst* i : INSTANCES) {
+        // what fits promises (shape half, checked on the CPU) is what is compiled, on the tail tile too
+        for (const SamplerInst* t : {i, i->tail2 ? i->tail2 : i})
+            if (!t->launch[M_SAMPLE] || !t->launch[M_EPS] || (t->launch[M_POSE] != nullptr) != i->pose) return false;
+        if (i->wave8 && !i->wave8->launch[M_SAMPLE]) return false;
+    }
+    return true;
+}
+static_assert(instances_consistent(), "an instance's fits and its compiled kernel modes disagree");
+
+// Scratch for dpk_eps's per-pose projections [N][NL][D].  Where the schedule holds dpk_sample's they are all the
+// pool serves: at least 64 poses, refusals in poses.  Elsewhere it is counted in floats (gen_scratch).
+static int eps_scratch(dpk_handle* h, hipStream_t st, bool cap, int N, float** out) {
+    const size_t PP = h->w.inst->tp;
+    if (!sched_tps(h)) return gen_scratch(h, st, cap, (size_t)N * PP, out, "dpk_eps");
+    ScratchBuf buf;
+    ScratchStatus why;
+    const int rc = call_scratch(h, st, cap, (size_t)(cap ? N : std::max(N, 64)) * PP, "dpk_eps", buf, why);
+    *out = buf.p;
+    if (why == SCRATCH_NO_SPARE)
+        return fail(h, rc, "dpk_eps: a captured call needs a projection buffer of " + std::to_string(N) +
+                               " poses, and the spare holds " + std::to_string(buf.cap / PP) +
+                               "; make an uncaptured dpk_eps call of >= N poses before the capture");
+    if (why == SCRATCH_SHARED_TOO_SMALL)
+        return fail(h, rc, "dpk_eps: the captured calls of one stream share the buffer of the capture's "
+                           "first call (" + std::to_string(buf.cap / PP) + " poses); this one has " +
+                               std::to_string(N) + "; warm up with the largest N before capturing");
+    return rc;
+}
+
 // What dpk_eps, dpk_sample and dpk_pose do once their arguments and the handle's state have passed: the
 // per-pose masks cover the N poses (models/GraFormer.py:107-108 broadcasts [N,1,17]), the handle's device is
 // current, and an uncaptured call recycles what destroyed graphs have released.
@@ -716,14 +803,7 @@ int dpk_kernel_geometry(int* ppw, int* tpw, int* lds) {
 int dpk_create(const dpk_config* cfg, dpk_handle** out) {
     if (!cfg || !out) return DPK_E_INVALID;
     *out = nullptr;
-    // the compiled shape runs the persistent sampler; any other (hid_dim a multiple of n_head,
-    // n_pts <= 32, any num_layer) the generic path (dpk_generic.inc); DPK_FORCE_GENERIC=1 sends the
-    // compiled shape there too (tests compare the two)
-    const char* fg = getenv("DPK_FORCE_GENERIC");
     const bool pose_io = cfg->coords_in == CIN_POSE && cfg->coords_out == COUT_POSE;
-    const bool compiled = cfg->hid_dim == D && cfg->num_layers >= 1 && cfg->num_layers <= NL && cfg->n_head == NH &&
-                          cfg->n_pts == J && (pose_io || (cfg->coords_in == CIN && cfg->coords_out == COUT)) &&
-                          !(fg && atoi(fg) != 0);
     if (cfg->hid_dim < 2 || cfg->n_head < 1 || cfg->hid_dim % cfg->n_head != 0 || cfg->num_layers < 1 ||
         cfg->n_pts < 2 || cfg->n_pts > dpkg::GJ_MAX || cfg->coords_in < 1 || cfg->coords_out < 1)
         return DPK_E_UNSUPPORTED;
@@ -740,9 +820,19 @@ int dpk_create(const dpk_config* cfg, dpk_handle** out) {
     h->num_layers = cfg->num_layers;
     h->n_pts = cfg->n_pts;
     h->mask = cfg->n_pts >= 32 ? ~0u : (1u << cfg->n_pts) - 1u;   // every key attends (all-ones src_mask)
-    if (compiled) stage_init(h->stage, D, NH, J, cfg->num_layers, cfg->coords_in, cfg->coords_out, kind);
-    else {
-        h->gen = gen_new(cfg->hid_dim, cfg->n_head, cfg->n_pts, cfg->num_layers, cfg->coords_in, cfg->coords_out, kind);
+    stage_init(h->stage, cfg->hid_dim, cfg->n_head, cfg->n_pts, cfg->num_layers, cfg->coords_in, cfg->coords_out, kind);
+    // a shape an instance is compiled for runs the persistent sampler; any other (hid_dim a multiple of n_head,
+    // n_pts <= 32) the per-op path.  DPK_FORCE_GENERIC=1 sends every shape there, DPK_GEN_FUSED=0 the widths
+    // other than the shipped one (A/B; tests compare the two paths)
+    const char* fg = getenv("DPK_FORCE_GENERIC");
+    const char* fe = getenv("DPK_GEN_FUSED");
+    const bool no_inst = fg && atoi(fg) != 0, no_widths = fe && atoi(fe) == 0;
+    for (const SamplerInst* i : INSTANCES)
+        if (!h->w.inst && !no_inst && !(no_widths && i != &dpk::INST) &&
+            i->fits(cfg->hid_dim, cfg->n_head, cfg->n_pts, cfg->num_layers, cfg->coords_in, cfg->coords_out, kind))
+            h->w.inst = i;
+    if (!h->w.inst) {
+        h->gen = gen_new(h->stage);
         h->pool.replaced = gen_scratch_replaced;   // its recorded loops are keyed by scratch address
         h->pool.ctx = h->gen;
     }
@@ -780,10 +870,8 @@ int dpk_create(const dpk_config* cfg, dpk_handle** out) {
 void dpk_destroy(dpk_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
-    if (h->arena) (void)hipFree(h->arena);
-    if (h->arena16) (void)hipFree(h->arena16);
-    if (h->arenabf) (void)hipFree(h->arenabf);
-    if (h->temb) (void)hipFree(h->temb);
+    for (void* p : {(void*)h->w.arena, (void*)h->w.temb, (void*)h->w.arena16, (void*)h->w.arenabf})
+        if (p) (void)hipFree(p);
     if (h->tproj_zero) (void)hipFree(h->tproj_zero);
     if (h->flags) (void)hipFree(h->flags);
     gen_free(h->gen);
@@ -813,13 +901,13 @@ const char* dpk_last_error(const dpk_handle* h) { return h ? h->err.c_str() : "n
 // until dpk_set_graph).  Weights and graphs are loaded rarely, so everything is repacked every time.
 static int pack_upload(dpk_handle* h) {
     if (h->gen) return gen_upload(h, h->gen);
-    dpk::pack_model(h->stage, h->pk, true);
+    h->w.inst->pack(h->stage, h->w.pk, h->w.inst->half_modes);
     return upload(h);
 }
 
 int dpk_set_graph(dpk_handle* h, const float* adj) {
     if (!h || !adj) return fail(h, DPK_E_INVALID, "dpk_set_graph: null argument");
-    stage_set_graph(h->gen ? h->gen->s : h->stage, adj);
+    stage_set_graph(h->stage, adj);
     h->have_graph = true;
     return h->have_weights ? pack_upload(h) : DPK_OK;
 }
@@ -847,15 +935,15 @@ int dpk_load_weights(dpk_handle* h, const char* const* names, const float* const
     for (int i = 0; i < n; ++i)
         if (!names[i] || !ptrs[i]) return fail(h, DPK_E_INVALID, "dpk_load_weights: null entry");
     std::string err;
-    if (!stage_load(h->gen ? h->gen->s : h->stage, names, ptrs, numels, n, err))
+    if (!stage_load(h->stage, names, ptrs, numels, n, err))
         return fail(h, DPK_E_WEIGHTS, "dpk_load_weights: " + err);
     h->have_weights = true;
     const int rc = pack_upload(h);
     if (rc || h->gen || h->kind == 0) return rc;
     // the pose backbone adds no timestep projection: a zero row per layer (E_CHEB1 adds +0)
     if (!h->tproj_zero) {
-        HIPCHK(h, hipMalloc(&h->tproj_zero, (size_t)NL * D * 4));
-        HIPCHK(h, hipMemset(h->tproj_zero, 0, (size_t)NL * D * 4));
+        HIPCHK(h, hipMalloc(&h->tproj_zero, h->w.inst->tp * 4));
+        HIPCHK(h, hipMemset(h->tproj_zero, 0, h->w.inst->tp * 4));
     }
     return DPK_OK;
 }
@@ -916,7 +1004,7 @@ int dpk_set_schedule(dpk_handle* h, const float* abar, int n_alpha, const int* s
         sched_free(s);
         return fail(h, DPK_E_HIP, std::string("dpk_set_schedule: coef upload: ") + hipGetErrorString(e));
     }
-    if (h->have_weights && !h->gen) {   // the generic path computes its projections per call
+    if (h->have_weights && sched_tps(h)) {   // every other handle computes its projections per call
         const int rc = sched_compute_tps(h, s);
         if (rc) {
             sched_free(s);
@@ -936,10 +1024,10 @@ static int check_ready(dpk_handle* h, int kind = 0) {
                                          : "GCNpose handle (coords 2->3): use dpk_pose");
     if (!h->have_graph) return fail(h, DPK_E_STATE, "graph (adjacency) not set");
     if (!h->have_weights) return fail(h, DPK_E_STATE, "weights not loaded");
-    if (h->gen && h->gemm_mode != 0)
+    if (!(h->w.inst && h->w.inst->half_modes) && h->gemm_mode != 0)
         return fail(h, DPK_E_UNSUPPORTED, "generic-shape path (model shape other than hid 96 / 4 heads / 17 joints): "
                                           "fp32 GEMMs only (gemm mode 0)");
-    if (h->gemm_mode == 1 && !h->pk.w16_ok)
+    if (h->gemm_mode == 1 && !h->w.pk.w16_ok)
         return fail(h, DPK_E_UNSUPPORTED, "gemm mode 1 (3x fp16): a GEMM weight has |w| >= 1015, outside the split-fp16 "
                                           "packing range; use gemm mode 0 (fp32)");
     return DPK_OK;
@@ -955,25 +1043,12 @@ int dpk_eps(dpk_handle* h, const float* x, const float* t, float* eps, int N, vo
     bool cap = false;
     if ((rc = enter_call(h, N, "dpk_eps", st, &cap))) return rc;
     if (h->gen) return gen_eps(h, x, t, eps, N, st, cap);
-    // per-pose projections [N][NL][D]; buffers of at least 64 poses (the capacities in poses are whole)
-    constexpr size_t PP = (size_t)NL * D;
-    ScratchBuf buf;
-    ScratchStatus why;
-    if ((rc = call_scratch(h, st, cap, (size_t)(cap ? N : std::max(N, 64)) * PP, "dpk_eps", buf, why))) {
-        if (why == SCRATCH_NO_SPARE)
-            return fail(h, rc, "dpk_eps: a captured call needs a projection buffer of " + std::to_string(N) +
-                                   " poses, and the spare holds " + std::to_string(buf.cap / PP) +
-                                   "; make an uncaptured dpk_eps call of >= N poses before the capture");
-        if (why == SCRATCH_SHARED_TOO_SMALL)
-            return fail(h, rc, "dpk_eps: the captured calls of one stream share the buffer of the capture's "
-                               "first call (" + std::to_string(buf.cap / PP) + " poses); this one has " +
-                                   std::to_string(N) + "; warm up with the largest N before capturing");
-        return rc;
-    }
-    hipLaunchKernelGGL(temb_kernel, dim3(N), dim3(256), 0, st, h->temb, t, 1, buf.p);
+    float* tp = nullptr;             // per-pose projections [N][NL][D]
+    if ((rc = eps_scratch(h, st, cap, N, &tp))) return rc;
+    h->w.inst->temb(h->w.temb, t, 1, N, tp, st);
     HIPCHK(h, hipGetLastError());
     return profiled(h, st, cap, "dpk_eps", [&] {
-        return launch_sampler<M_EPS>(h, st, eps_args(h, h->arena, buf.p, x, eps, N), cap);
+        return launch_sampler(h, M_EPS, st, eps_args(h, h->w.arena, tp, x, eps, N), cap);
     });
 }
 
@@ -991,15 +1066,20 @@ int dpk_sample_noise(dpk_handle* h, const float* x, float* out, float* xs, float
     Sched* sc = h->sched;
     if (!sc) return fail(h, DPK_E_STATE, "schedule not set");
     if (N == 0) return DPK_OK;
-    if (!h->gen && sc->tps_gen != h->weights_gen)
+    if (sched_tps(h) && sc->tps_gen != h->weights_gen)
         return fail(h, DPK_E_STATE, "dpk_sample: schedule projections are stale");
     hipStream_t st = (hipStream_t)stream;
     bool cap = false;
     if ((rc = enter_call(h, N, "dpk_sample", st, &cap))) return rc;
     if (!cap) sched_sweep(h);
     if (h->gen) return gen_sample(h, sc, x, out, xs, x0s, N, seed, noise, st, cap);
+    float* tps = sc->tps;            // per-step projections [K][NL][D]: the schedule's, or this call's
+    if (!sched_tps(h)) {
+        if ((rc = gen_scratch(h, st, cap, (size_t)sc->K * h->w.inst->tp, &tps, "dpk_sample"))) return rc;
+        h->w.inst->temb(h->w.temb, sc->coef + 5, 6, sc->K, tps, st);
+    }
     if (xs) HIPCHK(h, hipMemcpyAsync(xs, x, (size_t)N * PE * 4, hipMemcpyDeviceToDevice, st));
-    SampleArgs a = sample_args(h, h->arena, sc->tps, sc, x, out, xs, x0s, N, seed, noise);
+    SampleArgs a = sample_args(h, h->w.arena, tps, sc, x, out, xs, x0s, N, seed, noise);
 #if DPK_TRACE
     if (h->trace_step >= 0) {
         const size_t len = (size_t)((N + P - 1) / P) * tile_waves(h) * TRACE_SLOTS;
@@ -1013,7 +1093,7 @@ int dpk_sample_noise(dpk_handle* h, const float* x, float* out, float* xs, float
     a.trace = h->trace_step >= 0 ? h->trace : nullptr;
     a.trace_step = h->trace_step;
 #endif
-    rc = profiled(h, st, cap, "dpk_sample", [&] { return launch_sampler<M_SAMPLE>(h, st, a, cap); });
+    rc = profiled(h, st, cap, "dpk_sample", [&] { return launch_sampler(h, M_SAMPLE, st, a, cap); });
     return rc ? rc : sched_note_use(h, sc, st, cap);
 }
 
@@ -1030,7 +1110,7 @@ int dpk_pose(dpk_handle* h, const float* x2d, float* xyz, float* uvxyz, int N, i
     if ((rc = enter_call(h, N, "dpk_pose", st, &cap))) return rc;
     if (h->gen) return gen_pose(h, x2d, xyz, uvxyz, N, H, root_mode, st, cap);
     return profiled(h, st, cap, "dpk_pose", [&] {
-        return launch_sampler<M_POSE>(h, st, pose_args(h, h->arena, h->tproj_zero, x2d, xyz, uvxyz, N, H, root_mode), cap);
+        return launch_sampler(h, M_POSE, st, pose_args(h, h->w.arena, h->tproj_zero, x2d, xyz, uvxyz, N, H, root_mode), cap);
     });
 }
 
@@ -1046,7 +1126,7 @@ int dpk_set_tile_waves(dpk_handle* h, int waves) {
     if (!h) return DPK_E_INVALID;
     if (waves != 0 && waves != 4 && waves != 8)
         return fail(h, DPK_E_INVALID, "dpk_set_tile_waves: waves must be 0 (the GEMM mode's default), 4 or 8");
-    if (waves == 8 && h->gen)
+    if (waves == 8 && !(h->w.inst && h->w.inst->wave8))
         return fail(h, DPK_E_UNSUPPORTED, "dpk_set_tile_waves: the 8-wave tile is compiled for hid 96 / 4 heads / 17 joints");
     h->tile_waves = waves;
     return DPK_OK;
@@ -1129,11 +1209,11 @@ int dpk_debug_resources(dpk_handle* h, int* out, int n) {
         tracked += c->tracked ? 1 : 0;
         released += (c->tracked && c->released.load()) ? 1 : 0;
     }
-    // the pool's spare: in poses of dpk_eps projections on the shipped shape, in KiB on the generic path
+    // the pool's spare: in poses of dpk_eps projections on the shipped shape (sched_tps), else in KiB
     const size_t spare = h->pool.spare.cap;
     const int v[8] = {(int)h->caps.size(), tracked, released, (int)h->slot_free.size(), retired,
-                      h->gen ? 0 : (int)(spare / ((size_t)NL * D)), gen_graph_count(h->gen),
-                      h->gen ? (int)((spare * 4) >> 10) : 0};
+                      sched_tps(h) ? (int)(spare / h->w.inst->tp) : 0, gen_graph_count(h->gen),
+                      sched_tps(h) ? 0 : (int)((spare * 4) >> 10)};
     for (int i = 0; i < n && i < 8; ++i) out[i] = v[i];
     return DPK_OK;
 }

@@ -1,8 +1,9 @@
 // dpk_sampler.inc — the sampler kernel and its device phases for one tile size and model width.
-// Included by dpk_kernels.hip six times, each inside a namespace of its own: dpk with DPK_P 4 (68-row tiles,
-// the main grid) and dpk2 with DPK_P 2 (34-row tiles for the last, partial round of a large batch) at the
-// shipped shape (hid 96 / 4 heads); dpkw / dpkw4 (DPK_D 128, DPK_NH 8 / 4, DPK_P 2) and dpkn / dpkn4
-// (DPK_D 64, DPK_NH 2 / 4, DPK_P 4), the fused samplers of the other widths (dpk_generic.inc).  The shape,
+// Included by dpk_kernels.hip seven times, each inside a namespace of its own: dpk with DPK_P 4 (68-row tiles,
+// the main grid), dpk8 (the same tile on 8 waves, DPK_NW 8) and dpk2 with DPK_P 2 (34-row tiles for the last,
+// partial round of a large batch) at the shipped shape (hid 96 / 4 heads); dpkw / dpkw4 (DPK_D 128, DPK_NH
+// 8 / 4, DPK_P 2) and dpkn / dpkn4 (DPK_D 64, DPK_NH 2 / 4, DPK_P 4), the samplers of the other widths; the host
+// reaches every one through the instance table (dpk_kernels.hip: INSTANCES).  The shape,
 // tile, LDS-carve and arena-layout constants are dpk_layout.inc's (shared with the host packer,
 // dpk_pack.inc); everything here depends on P only through P, R and the LDS carve, and on the width through
 // D, NH and those constants.

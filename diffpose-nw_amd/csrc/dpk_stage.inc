@@ -1,7 +1,7 @@
 // dpk_stage.inc — the host staging of one model, for any shape: its weights as row-major W_eff[k][n] blocks
 // and its graph's Chebyshev terms in one float arena, filled from a state_dict and an adjacency.  Every
-// handle holds one (dpk_handle for the shipped shape, GenModel for the others); the generic path's per-op
-// kernels read a device copy of it, and each sampler instance packs its own arena from it (dpk_pack.inc).
+// handle holds one (dpk_handle::stage); the per-op path's kernels read a device copy of it, and each sampler
+// instance packs its own arena from it (dpk_pack.inc).
 // Plain C++ (no HIP), so a CPU-only build compiles it too (tests/c/dpk_pack_check.cpp).
 #include <math.h>
 #include <stdint.h>
@@ -33,6 +33,24 @@ struct Packed {
     std::vector<uint16_t> abf;   // bf16 GEMM weights (gemm mode 2), same layout
     bool sparse = false;         // the adjacency fits the compiled H36M Chebyshev pattern (sparse kernels)
     bool w16_ok = true;          // the GEMM weights fit the split-fp16 packing (|w| < 1015)
+};
+
+// The shape and pack half of a sampler instance's descriptor (SHAPE in dpk_genfused.inc, one per instance
+// namespace; SamplerInst in dpk_kernels.hip adds the launch half)
+struct InstShape {
+    int D, NH, J, NL;            // hid_dim, n_head, n_pts, the most layers a launch runs
+    int P, NW, NT, lds_bytes;    // poses, waves and threads per workgroup; static LDS
+    size_t tp;                   // floats of timestep projections per step (sample) or pose (eps): NL * D
+    bool half_modes;             // has the gemm mode 1 and 2 kernels and arenas
+    bool pose;                   // has the GCNpose kernels (coords 2 -> 3)
+    int cin, cout;               // GCNdiff coords
+    size_t arena_floats, temb_floats, arena16_bytes, arenabf_bytes;   // the half-width two: 0 without half_modes
+    void (*pack)(const Stage& s, Packed& out, bool half_modes);
+    // does this instance run a model of this shape?  kind 1 (GCNpose) is coords 2 -> 3 by definition
+    bool fits(int Dm, int Hm, int Jm, int Lm, int cin_, int cout_, int kind) const {
+        return Dm == D && Hm == NH && Jm == J && Lm >= 1 && Lm <= NL &&
+               (kind == 0 ? cin_ == cin && cout_ == cout : pose);
+    }
 };
 
 static void stage_init(Stage& s, int D, int H, int J, int L, int cin, int cout, int kind) {

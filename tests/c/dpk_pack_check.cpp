@@ -1,16 +1,19 @@
 // CPU check of the host weight packer: the staging (dpk_stage.inc) and every sampler instance's
 // pack_model (dpk_pack.inc over dpk_layout.inc) on state dicts from a fixed integer LCG.  Prints one
 // FNV-1a-64 digest per packed buffer; tests/test_pack_cpu.py builds this with the host sanitizers and
-// compares the digests with the ones recorded from the loaders this packer replaced.
+// compares the digests with the ones recorded from the loaders this packer replaced.  Also checks which
+// configs the instance table accepts (the shape halves of its descriptors); a failure there is the exit code.
 // Plain C++, no HIP: clang++ -std=c++17 -ffp-contract=off -fsanitize=address,undefined
 #include <stdio.h>
 
 #include "../../diffpose-nw_amd/csrc/dpk_stage.inc"
 
+// the table's instances (dpk_kernels.hip: INSTANCES), each one's layout, packer and the shape half of its
+// descriptor (SHAPE, dpk_genfused.inc)
 #define DPK_P 4
 namespace dpk {
 #include "../../diffpose-nw_amd/csrc/dpk_layout.inc"
-#include "../../diffpose-nw_amd/csrc/dpk_pack.inc"
+#include "../../diffpose-nw_amd/csrc/dpk_genfused.inc"
 }  // namespace dpk
 #undef DPK_P
 #undef DPK_D
@@ -20,8 +23,14 @@ namespace dpk {
 #define DPK_NH 8
 namespace dpkw {
 #include "../../diffpose-nw_amd/csrc/dpk_layout.inc"
-#include "../../diffpose-nw_amd/csrc/dpk_pack.inc"
+#include "../../diffpose-nw_amd/csrc/dpk_genfused.inc"
 }  // namespace dpkw
+#undef DPK_NH
+#define DPK_NH 4
+namespace dpkw4 {
+#include "../../diffpose-nw_amd/csrc/dpk_layout.inc"
+#include "../../diffpose-nw_amd/csrc/dpk_genfused.inc"
+}  // namespace dpkw4
 #undef DPK_P
 #undef DPK_D
 #undef DPK_NH
@@ -30,8 +39,15 @@ namespace dpkw {
 #define DPK_NH 2
 namespace dpkn {
 #include "../../diffpose-nw_amd/csrc/dpk_layout.inc"
-#include "../../diffpose-nw_amd/csrc/dpk_pack.inc"
+#include "../../diffpose-nw_amd/csrc/dpk_genfused.inc"
 }  // namespace dpkn
+#undef DPK_NH
+#define DPK_NH 4
+namespace dpkn4 {
+#include "../../diffpose-nw_amd/csrc/dpk_layout.inc"
+#include "../../diffpose-nw_amd/csrc/dpk_genfused.inc"
+}  // namespace dpkn4
+static const InstShape* const SHAPES[] = {&dpk::SHAPE, &dpkw::SHAPE, &dpkw4::SHAPE, &dpkn::SHAPE, &dpkn4::SHAPE};
 
 // ---- inputs: state dicts and adjacencies from a fixed integer LCG (no file input) ----
 struct Lcg {
@@ -193,15 +209,35 @@ static int run_failed_loads() {
     return 0;
 }
 
+// (h) which configs the table's entries accept: every compiled GCNdiff shape exactly one, GCNpose the shipped
+// entry only, anything else none
+static int run_table_fits() {
+    auto accepts = [](int D, int H, int J, int L, int kind) {      // bit i: entry i accepts
+        int bits = 0;
+        for (int i = 0; i < 5; ++i)
+            if (SHAPES[i]->fits(D, H, J, L, kind ? 2 : 5, kind ? 3 : 5, kind)) bits |= 1 << i;
+        return bits;
+    };
+    static const int shapes[5][2] = {{96, 4}, {128, 8}, {128, 4}, {64, 2}, {64, 4}};
+    bool ok = true;
+    for (int i = 0; i < 5; ++i)
+        for (int L = 1; L <= 5; ++L) ok = ok && accepts(shapes[i][0], shapes[i][1], 17, L, 0) == 1 << i;
+    for (int L = 1; L <= 5; ++L) ok = ok && accepts(96, 4, 17, L, 1) == 1;
+    ok = ok && accepts(48, 4, 16, 1, 0) == 0 && accepts(96, 4, 17, 6, 0) == 0 && accepts(128, 8, 17, 5, 1) == 0;
+    printf("h-table ok=%d\n", (int)ok);
+    return ok ? 0 : 1;
+}
+
 int main() {
     const std::vector<float> h36m = make_adjacency(), dense = make_adjacency(3, 6);
     int rc = 0;
-    rc |= run("a", 96, 4, 5, 0, 1, h36m, false, true, dpk::pack_model);
-    rc |= run("b", 96, 4, 3, 0, 2, dense, false, true, dpk::pack_model);
-    rc |= run("c", 96, 4, 4, 1, 3, h36m, false, true, dpk::pack_model);
-    rc |= run("d", 96, 4, 5, 0, 1, h36m, true, true, dpk::pack_model);
-    rc |= run("e", 128, 8, 3, 0, 5, h36m, false, false, dpkw::pack_model);
-    rc |= run("f", 64, 2, 5, 0, 6, h36m, false, false, dpkn::pack_model);
+    rc |= run("a", 96, 4, 5, 0, 1, h36m, false, true, dpk::SHAPE.pack);
+    rc |= run("b", 96, 4, 3, 0, 2, dense, false, true, dpk::SHAPE.pack);
+    rc |= run("c", 96, 4, 4, 1, 3, h36m, false, true, dpk::SHAPE.pack);
+    rc |= run("d", 96, 4, 5, 0, 1, h36m, true, true, dpk::SHAPE.pack);
+    rc |= run("e", 128, 8, 3, 0, 5, h36m, false, false, dpkw::SHAPE.pack);
+    rc |= run("f", 64, 2, 5, 0, 6, h36m, false, false, dpkn::SHAPE.pack);
     rc |= run_failed_loads();
+    rc |= run_table_fits();
     return rc;
 }

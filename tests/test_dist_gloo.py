@@ -6,23 +6,15 @@ batch exactly (ragged and even shards, H>1), the metric all-reduce equals the
 single-process metric, and max-over-ranks timing.
 """
 import os
-import socket
 
 import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
+from helpers import free_port as _free_port
 
 WORLD = 2
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
 
 
 def _oracle_sampler():

@@ -22,8 +22,9 @@ import torch
 from conftest import record_delta
 from diffpose_amd.data import synthetic_batch
 from diffpose_amd.gcndiff import HipGCNdiff, adj_mx_from_edges
-from diffpose_amd.schedule import get_beta_schedule, make_seq
+from diffpose_amd.schedule import make_seq
 from diffpose_amd.weights import synthetic_state_dict
+from helpers import betas as _betas, mpjpe_mm as _mpjpe_mm
 
 pytestmark = pytest.mark.gpu
 
@@ -31,17 +32,6 @@ EPS_TOL_BF16 = 2.5e-2          # max |eps_hip - eps_ref|, one evaluation
 FINAL_TOL_BF16 = 4e-3          # max |x_hip - x_ref| after the whole loop
 MPJPE_TOL_BF16_MM = 1e-2       # |MPJPE_hip - MPJPE_ref| on the 1,024 frames (measured 2.93e-3 mm)
 MPJPE_FP32_BAR_MM = 1e-4       # the fp32 bar bf16 does not meet
-
-
-def _betas(T):
-    return torch.from_numpy(get_beta_schedule("linear", beta_start=1e-4, beta_end=1e-3,
-                                              num_diffusion_timesteps=T)).float()
-
-
-def _mpjpe_mm(out, targets):
-    o = np.asarray(out, np.float64)
-    xyz = o[:, :, 2:] - o[:, :1, 2:]
-    return float(np.mean(np.linalg.norm(xyz - np.asarray(targets, np.float64), axis=-1)) * 1000.0)
 
 
 @pytest.fixture(scope="module")

@@ -15,23 +15,13 @@ from conftest import record_delta
 from diffpose_amd import dist as D
 from diffpose_amd.data import shard_frames, synthetic_batch
 from diffpose_amd.gcndiff import HipGCNdiff, adj_mx_from_edges
-from diffpose_amd.schedule import get_beta_schedule, make_seq
+from diffpose_amd.schedule import make_seq
 from diffpose_amd.weights import synthetic_state_dict
+from helpers import betas as _betas, mpjpe_mm as _mpjpe_mm
 
 pytestmark = pytest.mark.gpu
 
 WORLD, FRAMES = 8, 8192
-
-
-def _betas(T=51):
-    return torch.from_numpy(get_beta_schedule("linear", beta_start=1e-4, beta_end=1e-3,
-                                              num_diffusion_timesteps=T)).float()
-
-
-def _mpjpe_mm(o, tgt):
-    o = np.asarray(o, np.float64)
-    xyz = o[:, :, 2:] - o[:, :1, 2:]
-    return float(np.mean(np.linalg.norm(xyz - np.asarray(tgt, np.float64), axis=-1)) * 1000.0)
 
 
 def test_config4_eight_shards_equal_unsharded_and_oracle():

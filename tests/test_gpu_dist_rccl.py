@@ -9,23 +9,15 @@ padded ragged shards).  The world-2 logic itself is covered on CPU over gloo
 """
 import json
 import os
-import socket
 import subprocess
 import sys
 
 import pytest
+from helpers import free_port as _free_port
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
 
 
 def _env():

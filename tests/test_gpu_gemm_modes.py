@@ -6,7 +6,6 @@ fp32 mode (test_gpu_parity.py): |eps - eps_ref| <= 5e-6, trajectories <= 5e-6 el
 |MPJPE_hip - MPJPE_ref| <= 1e-4 mm at the bench config.  The CPU emulation of the scheme
 (split-fp16 GEMM mode) gave max |d eps| 7.7e-7 and MPJPE delta 8.8e-7 mm.
 """
-import numpy as np
 import pytest
 import torch
 
@@ -16,33 +15,15 @@ from diffpose_amd import utils_diff
 from diffpose_amd.data import synthetic_batch
 from diffpose_amd.gcndiff import HipGCNdiff, adj_mx_from_edges
 from diffpose_amd.gcnpose import HipGCNpose
-from diffpose_amd.schedule import get_beta_schedule, make_seq
+from diffpose_amd.schedule import make_seq
 from diffpose_amd.weights import synthetic_state_dict
+from helpers import betas as _betas, maxdiff as _maxdiff, mpjpe_mm as _mpjpe_mm
 
 pytestmark = pytest.mark.gpu
 
 EPS_TOL = 5e-6
 TRAJ_TOL = 5e-6
 MPJPE_TOL_MM = 1e-4
-
-
-def _betas(T):
-    return torch.from_numpy(get_beta_schedule("linear", beta_start=1e-4, beta_end=1e-3,
-                                              num_diffusion_timesteps=T)).float()
-
-
-def _maxdiff(a, b):
-    a = a.detach().cpu().double().numpy() if torch.is_tensor(a) else np.asarray(a, np.float64)
-    b = b.detach().cpu().double().numpy() if torch.is_tensor(b) else np.asarray(b, np.float64)
-    assert a.shape == b.shape
-    return float(np.abs(a - b).max())
-
-
-def _mpjpe_mm(out, targets):
-    o = out.detach().cpu().double() if torch.is_tensor(out) else torch.from_numpy(np.asarray(out)).double()
-    xyz = o[:, :, 2:] - o[:, :1, 2:]
-    t = torch.from_numpy(np.asarray(targets)).double()
-    return float(torch.mean(torch.norm(xyz - t, dim=-1)) * 1000.0)
 
 
 @pytest.fixture(scope="module")

@@ -21,8 +21,9 @@ from conftest import record_delta
 
 from diffpose_amd.data import synthetic_batch
 from diffpose_amd.gcndiff import H36M_EDGES, HipGCNdiff, adj_mx_from_edges
-from diffpose_amd.schedule import get_beta_schedule, make_seq
+from diffpose_amd.schedule import make_seq
 from diffpose_amd.weights import synthetic_state_dict
+from helpers import betas as _betas, maxdiff as _maxdiff
 
 pytestmark = pytest.mark.gpu
 
@@ -30,18 +31,9 @@ TOL = 5e-6
 CHAIN16 = tuple((i, i + 1) for i in range(15))
 
 
-def _betas(T=51):
-    return torch.from_numpy(get_beta_schedule("linear", beta_start=1e-4, beta_end=1e-3,
-                                              num_diffusion_timesteps=T)).float()
-
-
 def _cfg(hid, heads, layers, npts, coords=(5, 5)):
     return ns(model=ns(hid_dim=hid, emd_dim=hid, coords_dim=list(coords), num_layer=layers, n_head=heads,
                        dropout=0.25, n_pts=npts))
-
-
-def _maxdiff(a, b):
-    return float((a.detach().cpu().double() - b.detach().cpu().double()).abs().max())
 
 
 def _inputs(n, npts, seed):
@@ -371,6 +363,27 @@ def test_fused_wide_sampler_matches_per_op_path(dev, monkeypatch, hid, heads):
         assert record_delta(_maxdiff(res["1"][2], torch.stack(rxs)), TOL)
         rz, _ = O.generalized_steps(x, ones, seq, fwd, _betas(), eta=0.7, noise=z)
         assert record_delta(_maxdiff(res["1"][3], rz[-1]), TOL)
+
+
+@pytest.mark.parametrize("hid,heads,layers,n", [(64, 2, 2, 5), (128, 8, 5, 3)])
+def test_one_partial_tile_matches_per_op_path(dev, monkeypatch, hid, heads, layers, n):
+    """The smallest calls that still reach a width's instance through the instance table: one partial tile of
+    each tile size (5 poses on dpkn's 4-pose tiles: a full tile and one pose; 3 on dpkw's 2-pose tiles), K = 3.
+    forward and sample equal the same model on the per-op path (DPK_GEN_FUSED=0) within the fp32 bar."""
+    x = _inputs(n, 17, seed=17 + hid)
+    t = torch.arange(n, dtype=torch.float32) * 7.0
+    ones = torch.ones(1, 1, 17, dtype=torch.bool)
+    sd = synthetic_state_dict(hid=hid, n_layers=layers)
+    res = {}
+    for fused in ("1", "0"):
+        monkeypatch.setenv("DPK_GEN_FUSED", fused)
+        m = HipGCNdiff(adj_mx_from_edges(), _cfg(hid, heads, layers, 17), device=dev)
+        m.load_state_dict(sd)
+        res[fused] = (m(x.to(dev), ones.to(dev), t.to(dev), 0),
+                      m.sample(x.to(dev), [0, 17, 34], _betas(), mask=ones.to(dev)))
+        m.close()
+    for a, b in zip(res["1"], res["0"]):
+        assert a.shape == x.shape and record_delta(_maxdiff(a, b), TOL)
 
 
 @pytest.mark.parametrize("hid,heads", [(128, 8), (64, 2)])

@@ -10,28 +10,23 @@ them from what the kernel achieves (every check reports its delta through
   * north-star bar: |MPJPE_hip - MPJPE_ref| <= 1e-4 mm at B=1024, K=50.
 The reference's own fp32-vs-fp64 gap on these inputs is 1.6e-5 mm / 1.2e-6 per element.
 """
-import numpy as np
 import pytest
 import torch
 
 from conftest import record_delta
 
-from diffpose_amd.schedule import get_beta_schedule, make_seq
+from diffpose_amd.schedule import make_seq
 from diffpose_amd.weights import synthetic_state_dict
 from diffpose_amd.data import synthetic_batch
 from diffpose_amd.gcndiff import HipGCNdiff, adj_mx_from_edges
 from diffpose_amd import utils_diff
+from helpers import betas as _betas, maxdiff as _maxdiff, mpjpe_mm as _mpjpe_mm
 
 pytestmark = pytest.mark.gpu
 
 EPS_TOL = 5e-6
 TRAJ_TOL = 5e-6
 MPJPE_TOL_MM = 1e-4
-
-
-def _betas(T):
-    return torch.from_numpy(get_beta_schedule("linear", beta_start=1e-4, beta_end=1e-3,
-                                              num_diffusion_timesteps=T)).float()
 
 
 @pytest.fixture(scope="module")
@@ -46,21 +41,6 @@ def model():
 @pytest.fixture(scope="module")
 def mask():
     return torch.ones(1, 1, 17, dtype=torch.bool, device="cuda:0")
-
-
-def _maxdiff(a, b):
-    a = a.detach().cpu().double().numpy() if torch.is_tensor(a) else np.asarray(a, np.float64)
-    b = b.detach().cpu().double().numpy() if torch.is_tensor(b) else np.asarray(b, np.float64)
-    assert a.shape == b.shape
-    return float(np.abs(a - b).max())
-
-
-def _mpjpe_mm(out, targets):
-    o = out.detach().cpu().double() if torch.is_tensor(out) else torch.from_numpy(np.asarray(out)).double()
-    xyz = o[:, :, 2:]
-    xyz = xyz - xyz[:, :1, :]
-    t = torch.from_numpy(np.asarray(targets)).double()
-    return float(torch.mean(torch.norm(xyz - t, dim=-1)) * 1000.0)
 
 
 def test_eps_vs_golden(model, mask, golden):

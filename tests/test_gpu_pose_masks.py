@@ -21,18 +21,14 @@ from conftest import record_delta
 from diffpose_amd import _lib
 from diffpose_amd.data import synthetic_batch
 from diffpose_amd.gcndiff import HipGCNdiff, adj_mx_from_edges
-from diffpose_amd.schedule import get_beta_schedule, make_seq
+from diffpose_amd.schedule import make_seq
 from diffpose_amd.weights import synthetic_state_dict
+from helpers import betas as _betas, maxdiff as _maxdiff
 
 pytestmark = pytest.mark.gpu
 
 EPS_TOL = 5e-6
 TRAJ_TOL = 5e-6
-
-
-def _betas(T):
-    return torch.from_numpy(get_beta_schedule("linear", beta_start=1e-4, beta_end=1e-3,
-                                              num_diffusion_timesteps=T)).float()
 
 
 @pytest.fixture(scope="module")
@@ -60,10 +56,6 @@ def _masks(n, seed=5):
         if not m[i].any():
             m[i, 0, i % 17] = True
     return torch.from_numpy(m)
-
-
-def _maxdiff(a, b):
-    return float((a.detach().cpu().double() - b.detach().cpu().double()).abs().max())
 
 
 def test_eps_per_pose_masks_vs_oracle(model):

@@ -18,15 +18,11 @@ import torch
 
 from diffpose_amd.data import synthetic_batch
 from diffpose_amd.gcndiff import HipGCNdiff, adj_mx_from_edges
-from diffpose_amd.schedule import get_beta_schedule, make_seq
+from diffpose_amd.schedule import make_seq
 from diffpose_amd.weights import synthetic_state_dict
+from helpers import betas as _betas
 
 pytestmark = pytest.mark.gpu
-
-
-def _betas(T=51):
-    return torch.from_numpy(get_beta_schedule("linear", beta_start=1e-4, beta_end=1e-3,
-                                              num_diffusion_timesteps=T)).float()
 
 
 @pytest.fixture(scope="module")

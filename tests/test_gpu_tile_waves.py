@@ -16,18 +16,13 @@ from conftest import record_delta
 
 from diffpose_amd.data import synthetic_batch
 from diffpose_amd.gcndiff import H36M_EDGES, HipGCNdiff, adj_mx_from_edges
-from diffpose_amd.schedule import get_beta_schedule
 from diffpose_amd.weights import synthetic_state_dict
+from helpers import betas as _betas, maxdiff as _maxdiff
 
 pytestmark = pytest.mark.gpu
 
 TOL = {"fp32": 5e-6, "f16x3": 5e-6, "bf16": 4e-3}
 MODES = ("fp32", "f16x3", "bf16")
-
-
-def _betas(T=51):
-    return torch.from_numpy(get_beta_schedule("linear", beta_start=1e-4, beta_end=1e-3,
-                                              num_diffusion_timesteps=T)).float()
 
 
 def _seq(k):
@@ -37,10 +32,6 @@ def _seq(k):
 
 def _ones():
     return torch.ones(1, 1, 17, dtype=torch.bool, device="cuda:0")
-
-
-def _maxdiff(a, b):
-    return float((a.detach().cpu().double() - b.detach().cpu().double()).abs().max())
 
 
 @pytest.fixture(scope="module")

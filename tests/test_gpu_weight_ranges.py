@@ -22,6 +22,7 @@ import torch
 from diffpose_amd.gcndiff import HipGCNdiff, adj_mx_from_edges
 from diffpose_amd.schedule import get_beta_schedule
 from diffpose_amd.weights import reference_init_state_dict, synthetic_state_dict
+from helpers import mpjpe_mm as _mpjpe_mm
 
 pytestmark = pytest.mark.gpu
 
@@ -33,12 +34,6 @@ def _weights(name):
     if name.startswith("g9_refinit_seed"):
         return reference_init_state_dict(int(name[len("g9_refinit_seed"):].split(".")[0]))
     return synthetic_state_dict(seed=7)
-
-
-def _mpjpe_mm(o, tgt):
-    o = np.asarray(o, np.float64)
-    xyz = o[:, :, 2:] - o[:, :1, 2:]
-    return float(np.mean(np.linalg.norm(xyz - np.asarray(tgt, np.float64), axis=-1)) * 1000.0)
 
 
 @pytest.mark.parametrize("gemm", ["fp32", "f16x3"])

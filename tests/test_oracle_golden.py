@@ -20,6 +20,7 @@ from diffpose_amd.data import synthetic_batch, shard_frames, repeat_hypotheses
 from diffpose_amd.gcndiff import adj_mx_from_edges
 
 from conftest import GOLDEN
+from helpers import betas as _betas
 
 ATOL = 1e-6
 
@@ -99,11 +100,6 @@ def test_full_eps(golden, params, graph):
     _close(eps.numpy(), g["eps"])
     eps_m = O.gcndiff_forward(params, graph, x, torch.from_numpy(g["mask2"]), t)
     _close(eps_m.numpy(), g["eps_masked"])
-
-
-def _betas(T):
-    return torch.from_numpy(get_beta_schedule("linear", beta_start=1e-4, beta_end=1e-3,
-                                              num_diffusion_timesteps=T)).float()
 
 
 def test_trajectory_k10(golden, params, graph):

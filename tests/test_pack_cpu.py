@@ -12,7 +12,7 @@ CLANG = "/opt/rocm/lib/llvm/bin/clang++"     # the system g++ may predate _Float
 
 # FNV-1a-64 digests of the host buffers packed at commit dd74c60 (before the loaders were merged): cases
 # a-d by its dpk_set_graph + dpk_load_weights (shipped shape: hid 96 / 4 heads), e-f by its gen_set_graph +
-# gen_load + gen_fused_pack (dpkw: hid 128 / 8 heads; dpkn: hid 64 / 2 heads), on these inputs
+# gen_load + its fused-width packer (dpkw: hid 128 / 8 heads; dpkn: hid 64 / 2 heads), on these inputs
 EXPECTED = {
     # kind 0, 5 layers, H36M adjacency
     "a": "arena=868a614cfd64be86 temb=d837e1b2fd8a32d5 a16=c1a8b470f4a3ef27 abf=136d6b1554c65041 sparse=1 w16_ok=1",

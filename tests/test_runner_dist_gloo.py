@@ -10,23 +10,15 @@ the test also checks that each rank receives exactly its rows of the reference's
 draws.  The bar: bit-equal (p1, p2), per-action sums and epoch meters vs one process.
 """
 import os
-import socket
 
 import numpy as np
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
+from helpers import free_port as _free_port
 
 WORLD = 2
 ACT = ["Directions", "Eating", "Sitting", "Walking", "WalkDog"]
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
 
 
 def _batches():
