@@ -8,9 +8,9 @@
 #include "dpk_pack.inc"
 
 // the GCNpose kernels (coords 2 -> 3) are compiled for the shipped shape's 4-wave tiles alone
-constexpr InstShape SHAPE = {D, NH, J, NL, P, NW, NT, SM_FLOATS * 4, (size_t)NL * D, HALF_MODES, HALF_MODES && NW == 4,
-                             CIN, COUT, ARENA_FLOATS, TEMB_FLOATS, HALF_MODES ? ARENA16_BYTES : 0,
-                             HALF_MODES ? ARENA16_BYTES / 2 : 0, pack_model};
+constexpr InstShape SHAPE = {D, NH, J, NL, P, NW, NT, SM_FLOATS * 4, (size_t)NL * D, GEMM_MODES, MODE_BF16 && NW == 4,
+                             CIN, COUT, ARENA_FLOATS, TEMB_FLOATS, MODE_F16X3 ? ARENA16_BYTES : 0,
+                             MODE_BF16 ? ARENA16_BYTES / 2 : 0, pack_model};
 
 #ifdef __HIPCC__
 static void fused_temb(const float* temb, const float* t, int stride, int count, float* out, hipStream_t st) {
@@ -19,15 +19,18 @@ static void fused_temb(const float* temb, const float* t, int stride, int count,
 
 // One sample_kernel launch of `blocks` workgroups for the graph pattern (sparse: the compiled H36M one),
 // the noise source (the caller's draws, ZM = 1, or counter-based) and the GEMM mode gm (0 fp32 from W;
-// 1 f16x3 / 2 bf16 from W16, which only the instances with HALF_MODES have kernels for).
+// 1 f16x3 / 2 bf16 from W16: each compiled where the instance's descriptor has the mode, SHAPE.modes; a mode it
+// lacks never gets here, check_ready refuses it).
 template <int MODE, bool SP, int ZM>
 static void launch_gemm_mode(int gm, dim3 grid, size_t shmem, hipStream_t st, const SampleArgs& a, const float* W,
                              const char* W16) {
-    if constexpr (HALF_MODES) {
+    if constexpr (SHAPE.has_mode(1)) {
         if (gm == 1) {
             hipLaunchKernelGGL((sample_kernel<MODE, SP, 1, ZM>), grid, dim3(NT), shmem, st, a, W, W16);
             return;
         }
+    }
+    if constexpr (SHAPE.has_mode(2)) {
         if (gm == 2) {
             hipLaunchKernelGGL((sample_kernel<MODE, SP, 2, ZM>), grid, dim3(NT), shmem, st, a, W, W16);
             return;

@@ -147,7 +147,7 @@ namespace dpk2 {
 #include "dpk_genfused.inc"
 }  // namespace dpk2
 // The persistent sampler at a wider model (round 5): hid 128 / 8 heads (d_k 16), 2-pose tiles (4-pose
-// tiles of 128-wide rows do not fit 160 KB of LDS), fp32 GEMMs; a handle of that shape runs it instead of the
+// tiles of 128-wide rows do not fit 160 KB of LDS), fp32 or f16x3 GEMMs; a handle of that shape runs it instead of the
 // per-op launches of dpk_generic.inc
 #undef DPK_P
 #define DPK_P 2
@@ -264,7 +264,7 @@ struct InstWeights {
     Packed pk;                     // the arenas packed from the handle's staging (inst->pack), as uploaded
     float* arena = nullptr;        // device: packed weights + graph constants
     float* temb = nullptr;         // device: timestep-MLP weights
-    char* arena16 = nullptr;       // device: split-fp16 GEMM weights (gemm mode 1; instances with half_modes)
+    char* arena16 = nullptr;       // device: split-fp16 GEMM weights (gemm mode 1; instances that have the mode)
     char* arenabf = nullptr;       // device: bf16 GEMM weights (gemm mode 2), same layout
 };
 
@@ -313,6 +313,9 @@ static int fail(dpk_handle* h, int code, const std::string& msg) {
     if (h) h->err = msg;
     return code;
 }
+
+// The gemm modes the handle's path runs, bit m for mode m: its sampler instance's, or fp32 alone per op
+static int gemm_modes(const dpk_handle* h) { return h->w.inst ? h->w.inst->modes : 1; }
 
 // `launch` (returns a DPK code) on `st`, between an event pair when the handle is profiling (dpk_profile;
 // never under a capture)
@@ -494,9 +497,11 @@ static int upload(dpk_handle* h) {
     if (!w.temb) HIPCHK(h, hipMalloc(&w.temb, w.inst->temb_floats * 4));
     HIPCHK(h, hipMemcpy(w.arena, w.pk.arena.data(), w.inst->arena_floats * 4, hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(w.temb, w.pk.temb.data(), w.inst->temb_floats * 4, hipMemcpyHostToDevice));
-    if (w.inst->half_modes) {
+    if (w.inst->has_mode(1)) {
         if (!w.arena16) HIPCHK(h, hipMalloc(&w.arena16, w.inst->arena16_bytes));
         HIPCHK(h, hipMemcpy(w.arena16, w.pk.a16.data(), w.inst->arena16_bytes, hipMemcpyHostToDevice));
+    }
+    if (w.inst->has_mode(2)) {
         if (!w.arenabf) HIPCHK(h, hipMalloc(&w.arenabf, w.inst->arenabf_bytes));
         HIPCHK(h, hipMemcpy(w.arenabf, w.pk.abf.data(), w.inst->arenabf_bytes, hipMemcpyHostToDevice));
     }
@@ -735,7 +740,7 @@ DPK_LAUNCHER(dpk, M_POSE) DPK_LAUNCHER(dpk2, M_POSE)
 DPK_INST(dpk8, {launch_sample<M_SAMPLE>, nullptr, nullptr}, nullptr, nullptr, true)
 DPK_INST(dpk2, {launch_sample<M_SAMPLE>, launch_sample<M_EPS>, launch_sample<M_POSE>}, nullptr, nullptr, true)
 DPK_INST(dpk, {launch_sample<M_SAMPLE>, launch_sample<M_EPS>, launch_sample<M_POSE>}, &dpk8::INST, &dpk2::INST, true)
-// hid 128 / 8 and 4 heads (2-pose tiles), hid 64 / 2 and 4 heads (4-pose tiles): GCNdiff, fp32 GEMMs
+// hid 128 / 8 and 4 heads (2-pose tiles), hid 64 / 2 and 4 heads (4-pose tiles): GCNdiff, gemm modes 0 and 1
 DPK_INST(dpkw, {launch_sample<M_SAMPLE>, launch_sample<M_EPS>, nullptr}, nullptr, nullptr, false)
 DPK_INST(dpkw4, {launch_sample<M_SAMPLE>, launch_sample<M_EPS>, nullptr}, nullptr, nullptr, false)
 DPK_INST(dpkn, {launch_sample<M_SAMPLE>, launch_sample<M_EPS>, nullptr}, nullptr, nullptr, false)
@@ -901,7 +906,7 @@ const char* dpk_last_error(const dpk_handle* h) { return h ? h->err.c_str() : "n
 // until dpk_set_graph).  Weights and graphs are loaded rarely, so everything is repacked every time.
 static int pack_upload(dpk_handle* h) {
     if (h->gen) return gen_upload(h, h->gen);
-    h->w.inst->pack(h->stage, h->w.pk, h->w.inst->half_modes);
+    h->w.inst->pack(h->stage, h->w.pk, true);      // with the half-width arenas of the modes the instance has
     return upload(h);
 }
 
@@ -1024,9 +1029,16 @@ static int check_ready(dpk_handle* h, int kind = 0) {
                                          : "GCNpose handle (coords 2->3): use dpk_pose");
     if (!h->have_graph) return fail(h, DPK_E_STATE, "graph (adjacency) not set");
     if (!h->have_weights) return fail(h, DPK_E_STATE, "weights not loaded");
-    if (!(h->w.inst && h->w.inst->half_modes) && h->gemm_mode != 0)
-        return fail(h, DPK_E_UNSUPPORTED, "generic-shape path (model shape other than hid 96 / 4 heads / 17 joints): "
-                                          "fp32 GEMMs only (gemm mode 0)");
+    if (!(gemm_modes(h) >> h->gemm_mode & 1)) {
+        static const char* const NAMES[3] = {"0 (fp32)", "1 (f16x3)", "2 (bf16)"};
+        const Stage& s = h->stage;
+        return fail(h, DPK_E_UNSUPPORTED,
+                    std::string("gemm mode ") + NAMES[h->gemm_mode] + " is not available at hid " + std::to_string(s.D) +
+                        " / " + std::to_string(s.H) + " heads / " + std::to_string(s.J) + " joints" +
+                        (h->w.inst ? " (the persistent sampler of this shape has no kernels for it)"
+                                   : " (per-op path: fp32 GEMMs only)") +
+                        "; dpk_gemm_modes lists the modes of a handle");
+    }
     if (h->gemm_mode == 1 && !h->w.pk.w16_ok)
         return fail(h, DPK_E_UNSUPPORTED, "gemm mode 1 (3x fp16): a GEMM weight has |w| >= 1015, outside the split-fp16 "
                                           "packing range; use gemm mode 0 (fp32)");
@@ -1121,6 +1133,8 @@ int dpk_set_gemm_mode(dpk_handle* h, int mode) {
     h->gemm_mode = mode;
     return DPK_OK;
 }
+
+int dpk_gemm_modes(const dpk_handle* h) { return h ? gemm_modes(h) : 0; }
 
 int dpk_set_tile_waves(dpk_handle* h, int waves) {
     if (!h) return DPK_E_INVALID;

@@ -26,8 +26,16 @@ constexpr int CIN = 5;       // coords_dim[0]
 constexpr int COUT = 5;      // coords_dim[1]
 constexpr int PE = J * CIN;  // floats per pose (85)
 
-// the shipped shape's instances alone have the half-width-operand GEMM kernels (gemm modes 1, 2) and arenas
-constexpr bool HALF_MODES = D == 96 && NH == 4;
+// Which gemm modes the instance has kernels and an arena for, beside fp32 (mode 0).  Mode 1 (f16x3, the
+// half-width-operand GEMMs of dpk_sampler.inc) is parametrised on the width and compiled for every instance
+// unless its namespace sets DPK_F16X3 0 (an instance where it measured no faster than fp32, or did not fit its
+// registers); mode 2 (bf16) also changes attention, written for d_k 24: the shipped shape alone.
+#ifndef DPK_F16X3
+#define DPK_F16X3 1
+#endif
+constexpr bool MODE_F16X3 = DPK_F16X3 != 0;
+constexpr bool MODE_BF16 = D == 96 && NH == 4;
+constexpr int GEMM_MODES = 1 | (MODE_F16X3 ? 2 : 0) | (MODE_BF16 ? 4 : 0);   // bit m: gemm mode m
 
 // workgroup tile.  DPK_P (poses per workgroup) is set by the including file: 4 for the main sampler (one
 // workgroup per CU), 2 for the half-size tail tiles that balance the last round of a batch (launch_sampler)

@@ -57,14 +57,16 @@ static float pack16(uint16_t* dst, int Kreal, int Nreal, int KB32, int NC, F w) 
 
 // Everything the instance's kernels read, repacked from the staging `s` (a model of this instance's width,
 // 17 joints, at most NL layers; GCNdiff, or GCNpose with coords 2 -> 3): layers past s.L stay zero.
-// half_modes: also the split-fp16 and bf16 copies of the layer GEMMs' weights (gemm modes 1, 2) and w16_ok.
-static void pack_model(const Stage& s, Packed& out, bool half_modes) {
+// half: also the split-fp16 and bf16 copies of the layer GEMMs' weights, each where the instance has its gemm
+// mode (MODE_F16X3, MODE_BF16), and w16_ok.
+static void pack_model(const Stage& s, Packed& out, bool half) {
+    const bool f16 = half && MODE_F16X3, bf = half && MODE_BF16;
     const float* S = s.h.data();
     const int cin = s.cin, cout = s.cout;
     out.arena.assign(ARENA_FLOATS, 0.f);
     out.temb.assign(TEMB_FLOATS, 0.f);
-    out.a16.assign(half_modes ? ARENA16_BYTES / 2 : 0, 0);
-    out.abf.assign(half_modes ? ARENA16_BYTES / 4 : 0, 0);     // bf16 blocks: half the bytes
+    out.a16.assign(f16 ? ARENA16_BYTES / 2 : 0, 0);
+    out.abf.assign(bf ? ARENA16_BYTES / 4 : 0, 0);     // bf16 blocks: half the bytes
     float* A = out.arena.data();
     float w16max = 0.f;             // largest |64 w| of the split-fp16 GEMM weights
     for (int l = 0; l < s.L; ++l) {
@@ -88,12 +90,12 @@ static void pack_model(const Stage& s, Packed& out, bool half_modes) {
         pack_blocks(Lw + OFF_FC2, D2, D, KB_D2, NCD, w2);
         pack_blocks(Lw + OFF_C1, D3, D, KB_D3, NCD, wc1);
         pack_blocks(Lw + OFF_C2, D3, D, KB_D3, NCD, wc2);
-        if (half_modes) {           // the fp32 mode's operands, in both half-width packings
-            uint16_t* L16 = out.a16.data() + (size_t)l * LAYER16_BYTES / 2;
-            uint16_t* Lb = out.abf.data() + (size_t)l * LAYER16_BYTES / 4;
+        if (f16 || bf) {            // the fp32 mode's operands, in the half-width packings the instance reads
+            uint16_t* L16 = f16 ? out.a16.data() + (size_t)l * LAYER16_BYTES / 2 : nullptr;
+            uint16_t* Lb = bf ? out.abf.data() + (size_t)l * LAYER16_BYTES / 4 : nullptr;
             auto both = [&](int o16, int K, int N, int KB32, int NC, auto w) {
-                w16max = fmaxf(w16max, pack16(L16 + o16 / 2, K, N, KB32, NC, w));
-                (void)pack16<true>(Lb + o16 / 4, K, N, KB32, NC, w);
+                if (f16) w16max = fmaxf(w16max, pack16(L16 + o16 / 2, K, N, KB32, NC, w));
+                if (bf) (void)pack16<true>(Lb + o16 / 4, K, N, KB32, NC, w);
             };
             both(O16_QKV, D, D3, KB32_D, 3 * NCD, wqkv);
             both(O16_O, D, D, KB32_D, NCD, wo);

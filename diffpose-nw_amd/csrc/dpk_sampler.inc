@@ -758,11 +758,35 @@ __device__ __forceinline__ int pass_col(int ctp, int c, int rot) {
 #define DPK_HS_BF 3      // bf16 column-half GEMMs with K > 96: B ring slots
 #endif
 #ifndef DPK_PWQ16
-#define DPK_PWQ16 3      // f16x3 QKV: column tiles per pass (of the wave's 9)
+#define DPK_PWQ16 3      // f16x3 QKV at hid 96: column tiles per pass (of the wave's 9)
 #endif
 #ifndef DPK_PWF16
-#define DPK_PWF16 3      // f16x3 fc1: column tiles per pass (of the wave's 6)
+#define DPK_PWF16 3      // f16x3 fc1 at hid 96: column tiles per pass (of the wave's 6)
 #endif
+// The f16x3 column tiles per pass at each width, of the wave's 3 NCD / 2 (QKV), NCD (fc1) and NCD / 2 (O, fc2, the
+// two Chebyshev GEMMs) column tiles.  A pass holds NRW x PW accumulator tiles (NRW = 2 row tiles on 4-pose
+// workgroups, 1 on 2-pose ones) and an S-slot ring of PW hi + lo B fragments; a GEMM of several passes keeps its
+// converted A fragments (ar[KB32][NRW + 1], 8 VGPRs each).  hid 96: the round-5 table (6 accumulator tiles a
+// pass), for both graph patterns.  hid 64 (4-pose tiles, KB32_D = 2) and hid 128 (2-pose tiles, KB32_D = 4, one
+// row tile a wave): the sparse-graph kernels' table is the measured one (profiles/f16x3_widths_bench.txt) and
+// every one of them reports no scratch (make resources).  The dense-graph kernels spill whatever the table, as
+// the fp32 ones do (52 - 84 bytes of scratch a lane at these widths): theirs is narrowed to 3 (QKV) and 2 tiles a
+// pass, where their scratch is at the fp32 kernels' level (36 - 92 bytes; 228 - 484 with the sparse table).
+#ifndef DPK_PW64
+#define DPK_PW64 3, 4, 2     // hid 64, H36M-sparse graph: QKV (of 6), fc1 (of 4), the D-column GEMMs (of 2)
+#endif
+#ifndef DPK_PW128
+#define DPK_PW128 6, 4, 4    // hid 128, H36M-sparse graph: QKV (of 12), fc1 (of 8), the D-column GEMMs (of 4)
+#endif
+template <bool SPARSE>
+struct HPW {
+    static constexpr int W64[3] = {DPK_PW64}, W128[3] = {DPK_PW128}, DENSE[3] = {3, 2, 2};
+    static constexpr int pick(int i) { return !SPARSE ? DENSE[i] : D == 64 ? W64[i] : W128[i]; }
+    static constexpr int QKV = D == 96 ? DPK_PWQ16 : pick(0);
+    static constexpr int FC1 = D == 96 ? DPK_PWF16 : pick(1);
+    static constexpr int O = D == 96 ? 3 : pick(2), FC2 = O, CHEB = O;
+};
+static_assert(D == 96 || D == 64 || D == 128, "HPW: a pass table per compiled width");
 #ifndef DPK_PWF16_W8
 #define DPK_PWF16_W8 6   // f16x3 fc1 on 8 waves
 #endif
@@ -1097,9 +1121,9 @@ __device__ __forceinline__ void gemmh_wg(const float* A, int lda, const char* Bp
                                          const BPreH<G, sub_max(PW)>& pre, const float* AX = nullptr, int ldx = 0) {
     static_assert(NC % 2 == 0 && (NC / 2) % PW == 0 && (R == 68 || R == 34), "passes of PW column tiles");
     constexpr int NCW = NC / 2, NRW = R == 68 ? 2 : 1, NPASS = NCW / PW;
-    // ring slots: 3 (all of a K = 96 GEMM's k-blocks in flight; also for the 9-tile bf16 QKV pass) unless
-    // the pass is wide (registers); DPK_HS_BF for the bf16 K = 192 / 288 GEMMs (one 1 KiB fragment per
-    // tile and slot)
+    // ring slots: all of a K <= 96 GEMM's k-blocks in flight (3 at hid 96, also for the 9-tile bf16 QKV pass;
+    // 2 at hid 64), 3 for a longer K, unless the pass is wide (registers: 2); DPK_HS_BF for the bf16
+    // K = 192 / 288 GEMMs (one 1 KiB fragment per tile and slot).  Slot kb % S: S need not divide KB32
     constexpr int S = PW >= 6 ? ((G == 2 && KB32 == 3) ? 3 : 2)
                               : (KB32 <= 3 ? KB32 : (G == 2 ? (DPK_HS_BF < KB32 ? DPK_HS_BF : KB32) : 3));
     const int pr = gemm_pr(wave);
@@ -1114,7 +1138,7 @@ __device__ __forceinline__ void gemmh_wg(const float* A, int lda, const char* Bp
             gemmh_pass<G, NRW, PW, NC, KB32, MODE, XS2, S, 0, C0, NCS, NPW>(A, lda, AX, ldx, src, NRW * pr, ct0, rot,
                                                                             R - R % 16, dup, lane, e, pre, nullptr);
         } else {
-            // later passes reuse the first pass's converted A fragments (K = 96: KB32 = 3)
+            // later passes reuse the first pass's converted A fragments (K = D: KB32 = 2, 3 or 4)
             AFr<G> ar[KB32][NRW + 1];
             gemmh_pass<G, NRW, PW, NC, KB32, MODE, XS2, S, 1, C0, NCS, NPW>(A, lda, AX, ldx, src, NRW * pr, ct0, rot,
                                                                             R - R % 16, dup, lane, e, pre, ar);
@@ -1131,7 +1155,7 @@ __device__ __forceinline__ void gemmh_wg(const float* A, int lda, const char* Bp
         gemmh_pass<G, NRW, PW, NC, KB32, MODE, XS2, S, 0>(A, lda, AX, ldx, src, NRW * pr, ct0, rot, R - R % 16, dup,
                                                           lane, e, pre, nullptr);
     } else if constexpr (NSUB == 1) {
-        // later passes reuse the first pass's converted A fragments (K = 96: KB32 = 3)
+        // later passes reuse the first pass's converted A fragments (K = D: KB32 = 2, 3 or 4)
         AFr<G> ar[KB32][NRW + 1];
         gemmh_pass<G, NRW, PW, NC, KB32, MODE, XS2, S, 1>(A, lda, AX, ldx, src, NRW * pr, ct0, rot, R - R % 16, dup,
                                                           lane, e, pre, ar);
@@ -2258,8 +2282,9 @@ __global__ void __launch_bounds__(NT, 1) sample_kernel(SampleArgs a, const float
             // half-width-operand GEMM weights of this layer (gemm modes 1, 2; offh); block set X at O16_X / GH
             constexpr int GH = G16 ? G16 : 1;              // (instantiations with G16 = 0 never read LH)
             const char* LH = arena16 + offh<GH>(l, 0);
-            constexpr int PWQ = G16 == 2 ? 9 : (NSUB == 2 ? DPK_PWQ16_W8 : DPK_PWQ16);  // QKV column tiles per pass (f16x3: registers)
-            constexpr int PWF = G16 == 2 ? 6 : (NSUB == 2 ? DPK_PWF16_W8 : DPK_PWF16);  // fc1
+            // column tiles per pass of the half-width GEMMs (HPW; f16x3: registers)
+            constexpr int PWQ = G16 == 2 ? 9 : (NSUB == 2 ? DPK_PWQ16_W8 : HPW<SPARSE>::QKV);
+            constexpr int PWF = G16 == 2 ? 6 : (NSUB == 2 ? DPK_PWF16_W8 : HPW<SPARSE>::FC1);
             constexpr int GG = G16 == 2 ? 2 : 0;           // attention's and the graph products' arithmetic
             // ---- x = x + MHA(LN0(x))   (GraAttenLayer, GraFormer.py:94-95)
             {
@@ -2286,7 +2311,7 @@ __global__ void __launch_bounds__(NT, 1) sample_kernel(SampleArgs a, const float
             BAR();
             {
                 const EpiArgs e{XS, LDX, LW + OFF_BO, nullptr, 0, pose0, a.N - 1};
-                using HO = HGemm<GH, NCD, KB32_D, 3>;
+                using HO = HGemm<GH, NCD, KB32_D, HPW<SPARSE>::O>;
                 BPre<sub_max(NCD / 2)> pre;
                 typename HO::Pre preh;
                 auto o_pre = [&]() {
@@ -2360,7 +2385,7 @@ __global__ void __launch_bounds__(NT, 1) sample_kernel(SampleArgs a, const float
             {
                 const EpiArgs e{B1, LDX, nullptr, nullptr, 0, pose0, a.N - 1};
                 if constexpr (G16) {
-                    using H2 = HGemm<GH, NCD, KB32_D2, 3>;
+                    using H2 = HGemm<GH, NCD, KB32_D2, HPW<SPARSE>::FC2>;
                     const typename H2::Pre pre = H2::prefetch(LH + O16_FC2 / GH, wave, lane);
                     BAR();
                     if (DPK_RUN(16 | 256)) H2::template run<E_STORE_NB>(B2, LD2, LH + O16_FC2 / GH, wave, lane, e, pre);
@@ -2373,7 +2398,7 @@ __global__ void __launch_bounds__(NT, 1) sample_kernel(SampleArgs a, const float
             {
                 const float* tp = a.tproj + (MODE == M_SAMPLE ? (size_t)s * NL * D : 0) + l * D;
                 const EpiArgs e{B1, LDX, LW + OFF_BC1, tp, EPS_MODE ? NL * D : 0, pose0, a.N - 1};
-                using HC = HGemm<GH, NCD, KB32_D3, 3>;
+                using HC = HGemm<GH, NCD, KB32_D3, HPW<SPARSE>::CHEB>;
                 BPre<sub_max(NCD / 2)> pre;
                 typename HC::Pre preh;
                 auto c1_pre = [&]() {
@@ -2400,7 +2425,7 @@ __global__ void __launch_bounds__(NT, 1) sample_kernel(SampleArgs a, const float
             }
             {
                 const EpiArgs e{XS, LDX, LW + OFF_BC2, nullptr, 0, pose0, a.N - 1};
-                using HC = HGemm<GH, NCD, KB32_D3, 3>;
+                using HC = HGemm<GH, NCD, KB32_D3, HPW<SPARSE>::CHEB>;
                 BPre<sub_max(NCD / 2)> pre;
                 typename HC::Pre preh;
                 auto c2_pre = [&]() {

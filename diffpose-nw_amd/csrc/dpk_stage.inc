@@ -25,8 +25,8 @@ struct Stage {
 };
 
 // What a sampler instance's pack_model makes of a Stage: its weight arena and timestep-MLP arena in the
-// instance's layouts (dpk_layout.inc), the half-width copies of the GEMM weights where the instance has
-// gemm modes 1 and 2 (else empty), and what the host decides from the values
+// instance's layouts (dpk_layout.inc), the half-width copies of the GEMM weights for each of gemm modes 1 and 2
+// the instance has (else empty), and what the host decides from the values
 struct Packed {
     std::vector<float> arena, temb;
     std::vector<uint16_t> a16;   // split-fp16 GEMM weights (gemm mode 1)
@@ -41,11 +41,13 @@ struct InstShape {
     int D, NH, J, NL;            // hid_dim, n_head, n_pts, the most layers a launch runs
     int P, NW, NT, lds_bytes;    // poses, waves and threads per workgroup; static LDS
     size_t tp;                   // floats of timestep projections per step (sample) or pose (eps): NL * D
-    bool half_modes;             // has the gemm mode 1 and 2 kernels and arenas
+    int modes;                   // bit m set: has gemm mode m's kernels and arena (0 fp32: always; 1 f16x3; 2 bf16)
     bool pose;                   // has the GCNpose kernels (coords 2 -> 3)
     int cin, cout;               // GCNdiff coords
-    size_t arena_floats, temb_floats, arena16_bytes, arenabf_bytes;   // the half-width two: 0 without half_modes
-    void (*pack)(const Stage& s, Packed& out, bool half_modes);
+    size_t arena_floats, temb_floats, arena16_bytes, arenabf_bytes;   // the half-width two: 0 without their mode
+    // half: also the half-width arenas of the modes the instance has (and w16_ok); false: neither
+    void (*pack)(const Stage& s, Packed& out, bool half);
+    constexpr bool has_mode(int m) const { return m >= 0 && m < 3 && (modes >> m & 1); }
     // does this instance run a model of this shape?  kind 1 (GCNpose) is coords 2 -> 3 by definition
     bool fits(int Dm, int Hm, int Jm, int Lm, int cin_, int cout_, int kind) const {
         return Dm == D && Hm == NH && Jm == J && Lm >= 1 && Lm <= NL &&

@@ -203,6 +203,11 @@ class _HipModel:
         _lib.check(self._h, "dpk_set_gemm_mode", _lib.lib().dpk_set_gemm_mode(self._h, self.GEMM_MODES[mode]))
         self.gemm_mode = mode
 
+    def gemm_modes(self) -> int:
+        """The GEMM modes this model's calls run (see dpk_gemm_modes): bit m set for mode m of GEMM_MODES,
+        so 0b111 at hid 96 / 4 heads, 0b011 at the other persistent-sampler shapes and 0b001 per op."""
+        return int(_lib.lib().dpk_gemm_modes(self._h))
+
     TAIL_PLANS = {"four": 0, "two_pose": 1, "step_split": 2}
 
     def set_tail_plan(self, plan: str = "step_split") -> None:

@@ -84,8 +84,9 @@ int dpk_version(void);
  * persistent sampler; any other shape with hid_dim a multiple of n_head, n_pts <= 32 and coords
  * in == out (or [2,3]) runs the generic-shape path: the same model as per-op HIP kernels, or, for GCNdiff
  * at hid_dim 128 / n_head 8 or 4 and hid_dim 64 / n_head 2 or 4 on 17 joints (num_layer <= 5, coords [5,5]), the
- * persistent sampler compiled at that width (round 5); fp32 GEMMs only (dpk_set_gemm_mode 1/2 then fail
- * with DPK_E_UNSUPPORTED), per-stream scratch grown on demand; under a caller's stream capture the
+ * persistent sampler compiled at that width (round 5).  The four width instances run gemm modes 0 (fp32) and
+ * 1 (f16x3), the per-op kernels mode 0 alone; a call in a mode the handle's path lacks fails with
+ * DPK_E_UNSUPPORTED (dpk_gemm_modes says which it has).  Per-stream scratch grown on demand; under a caller's stream capture the
  * launches are recorded into the caller's graph from a capture-owned scratch (round 5; the first capture
  * of a size needs one uncaptured call of at least that size, else DPK_E_STATE).  Other shapes:
  * DPK_E_UNSUPPORTED. */
@@ -228,11 +229,18 @@ int dpk_gmm_sample_f64(const double* gmm_dev, const double* poses3d_dev, int n_s
  *           mode for the tolerance study of BASELINE config 3.
  * The input/output ChebConvs, LayerNorm, the softmax and the DDIM update stay fp32 in all modes, and
  * so do attention and the GraphNet products in modes 0 and 1.
- * Applies to later dpk_sample / dpk_eps / dpk_pose calls on this handle.  Range: mode 1 needs
- * every GEMM weight |w| < 1015 (else those calls return DPK_E_UNSUPPORTED) and GEMM inputs
- * (LayerNorm/attention/graph/Chebyshev outputs) below 65504 in magnitude; an overflow there
- * shows as non-finite outputs. */
+ * Applies to later dpk_sample / dpk_eps / dpk_pose calls on this handle.  Any of 0..2 is accepted
+ * here; which of them a handle runs depends on its shape (dpk_gemm_modes): all three at hid 96 / 4
+ * heads, modes 0 and 1 at hid 128 / 8 or 4 heads and hid 64 / 2 or 4 heads on the persistent sampler,
+ * mode 0 alone per op.  A call in a mode the handle lacks returns DPK_E_UNSUPPORTED, its message naming
+ * the mode and the shape.  Range: mode 1 needs every GEMM weight |w| < 1015 at every width (else those
+ * calls return DPK_E_UNSUPPORTED) and GEMM inputs (LayerNorm/attention/graph/Chebyshev outputs) below
+ * 65504 in magnitude; an overflow there shows as non-finite outputs. */
 int dpk_set_gemm_mode(dpk_handle* h, int mode);
+
+/* The gemm modes calls on this handle run: bit m set when mode m does (0b111 at hid 96 / 4 heads,
+ * 0b011 on the four other persistent-sampler shapes, 0b001 on a per-op handle; 0 for a null handle). */
+int dpk_gemm_modes(const dpk_handle* h);
 
 /* How dpk_sample balances a partial last round of tiles (4 poses per workgroup, one workgroup
  * per CU per round; not part of the reference interface, which has no tiles):
