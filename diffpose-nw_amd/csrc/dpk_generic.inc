@@ -14,7 +14,8 @@
 //   ResChebGC  cheb_basis -> gemm relu (+temb_proj) -> cheb_basis -> gemm relu (+x) (gcndiff.py:39-53)
 //   temb       one workgroup per timestep (gcndiff.py:15-33, :103-106); DDIM update per element.
 // Included by dpk_kernels.hip after the handle helpers (it uses dpk_handle, Sched, fail, HIPCHK).
-// Limits: n_pts <= 32 (one 32-bit key-mask word per pose), hid_dim a multiple of n_head.
+// Limits: n_pts <= 32 (one 32-bit key-mask word per pose), hid_dim a multiple of n_head and, for GCNdiff,
+// at least 4 (the timestep embedding divides by hid_dim / 2 - 1; dpk_create refuses 2 and 3).
 // Graph capture by the caller is refused on this path (its scratch is per-stream and grows on demand);
 // dpk_sample records its own K-step loop as a hipGraph instead (gen_sample).
 
@@ -22,6 +23,28 @@ namespace dpkg {
 
 constexpr int GJ_MAX = 32;
 enum { G_BIAS = 0, G_RELU = 1, G_RESID = 2, G_RESID_RELU = 3, G_RELU_TEMB = 4 };
+
+// The kernel forms gen_forward chooses between per call (from the shape, the batch and pointer alignment),
+// one bit each: GenModel::forms collects the bits of what was launched, dpk_debug_generic_forms reads and
+// clears them (test hook; diffpose_amd/gcndiff.py GENERIC_FORMS names the bits in this order).
+enum GenForm : unsigned {
+    F_GEMM_NARROW = 1u << 0,
+    F_GEMM_SK4 = 1u << 1,
+    F_GEMM_SK2 = 1u << 2,
+    F_GEMM_128_VEC = 1u << 3,
+    F_GEMM_128_SCALAR = 1u << 4,
+    F_GEMM_64_VEC = 1u << 5,
+    F_GEMM_64_SCALAR = 1u << 6,
+    F_GEMM_32_VEC = 1u << 7,
+    F_GEMM_32_SCALAR = 1u << 8,
+    F_ATTENTION_TT = 1u << 9,     // attention<STAGE, VEC>
+    F_ATTENTION_TF = 1u << 10,
+    F_ATTENTION_FF = 1u << 11,
+    F_GRAPH_T = 1u << 12,         // graph<STAGE>
+    F_GRAPH_F = 1u << 13,
+    F_CHEB_T = 1u << 14,          // cheb_basis<STAGE>
+    F_CHEB_F = 1u << 15,
+};
 
 // C[M][N] (row stride ldc) = epilogue(A[M][K] (lda) x W[K][N] + bias) on the fp32 matrix cores:
 // v_mfma_f32_16x16x4_f32 (exact fp32 products, fp32 accumulation).  A BM x 64 output tile per
@@ -297,7 +320,7 @@ __global__ void __launch_bounds__(256) layer_norm(const float* __restrict__ X, f
 // [q | k | v] (J x 3D floats each) staged in LDS with coalesced loads (STAGE; dynamic LDS ppb * J * RW
 // floats, used when that fits 64 KB), then one thread per (pose, head, query): scores / sqrt(dk), masked
 // keys -1e9, softmax, P.V, every sum in the reference's order per query (d ascending, then keys
-// ascending).  VEC (dk and D multiples of 4 and 8): 16-byte LDS reads and stores, LDS row stride
+// ascending).  VEC (dk and D multiples of 4 and 8, `out` 16-byte aligned): 16-byte LDS reads and stores, LDS row stride
 // RW = 3D + 4 (RW / 4 odd: the 16 lanes of a head reading rows q * RW hit disjoint bank quads);
 // otherwise RW = 3D + 1 (odd: distinct banks for scalar reads).
 template <bool STAGE, bool VEC>
@@ -384,7 +407,7 @@ __global__ void __launch_bounds__(256) attention(const float* __restrict__ qkv, 
 
 // Y[p][j][c] = sum_i Lm[j][i] X[p][i][c] (row strides ldx, ldy).  STAGE: one workgroup per pose, X_p and
 // Lm staged in LDS (dynamic, J*C + J*J floats), one thread per (j, 4 channels) when C, ldx, ldy are
-// multiples of 4 (16-byte LDS reads and global stores), else per (j, c); without STAGE one thread per
+// multiples of 4 and Y is 16-byte aligned (16-byte LDS reads and global stores), else per (j, c); without STAGE one thread per
 // output straight from global memory (poses too wide for 64 KB of LDS).  Sums over i ascending.
 template <bool STAGE>
 __global__ void __launch_bounds__(256) graph(const float* __restrict__ Lm, const float* __restrict__ X, int ldx,
@@ -407,7 +430,9 @@ __global__ void __launch_bounds__(256) graph(const float* __restrict__ Lm, const
         }
         for (int i = threadIdx.x; i < J * J; i += 256) ls[i] = Lm[i];
         __syncthreads();
-        if ((C & 3) == 0 && (ldy & 3) == 0) {
+        // 16-byte stores to Y: As and Gs sit after the Chebyshev operand's 3 max(hid, coords_in) floats a
+        // row, which is no multiple of 4 when the input is wider than hid_dim (coords 9 on hid 8)
+        if ((C & 3) == 0 && (ldy & 3) == 0 && (reinterpret_cast<uintptr_t>(Y) & 15) == 0) {
             const int C4 = C / 4;
             for (int o = threadIdx.x; o < J * C4; o += 256) {
                 const int j = o / C4, c4 = o - j * C4;
@@ -467,7 +492,9 @@ __global__ void __launch_bounds__(256) cheb_basis(const float* __restrict__ T1, 
             t2[i] = T2[i];
         }
         __syncthreads();
-        if ((C & 3) == 0) {
+        // 16-byte stores to Z: its rows are 3C floats, so the base decides (Zs sits after 2 M D floats of
+        // scratch: 8-byte aligned only with hid_dim and the row count odd)
+        if ((C & 3) == 0 && (reinterpret_cast<uintptr_t>(Z) & 15) == 0) {
             const int C4 = C / 4;
             for (int o = threadIdx.x; o < J * C4; o += 256) {
                 const int j = o / C4, c4 = o - j * C4;
@@ -649,6 +676,7 @@ struct GenModel {
     float* dev = nullptr;      // device arena
     std::vector<GenGraph> graphs;   // recorded K-step loops (at most GEN_GRAPHS, least recently used out)
     uint64_t use_clock = 0;
+    unsigned forms = 0;        // dpkg::GenForm bits of the kernel forms launched (or recorded) since the last read
 };
 constexpr size_t GEN_GRAPHS = 8;
 
@@ -667,6 +695,14 @@ static void gen_scratch_replaced(void* g, const float* old) { gen_drop_graphs(st
 static GenModel* gen_new(const Stage& s) { return new GenModel{s}; }
 
 static int gen_graph_count(const GenModel* g) { return g ? (int)g->graphs.size() : 0; }
+
+// the forms launched since the last call (0 without a GenModel), cleared
+static unsigned gen_take_forms(GenModel* g) {
+    if (!g) return 0;
+    const unsigned f = g->forms;
+    g->forms = 0;
+    return f;
+}
 
 static void gen_free(GenModel* g) {
     if (!g) return;
@@ -781,6 +817,7 @@ static void gen_forward(GenModel* g, hipStream_t st, const float* x, int N, cons
         auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
         const bool vec = K % 4 == 0 && Nn % 4 == 0 && al16(a) && al16(W + w);
         if (Nn <= 8 && (size_t)K * Nn * 4 <= 65536) {
+            g->forms |= dpkg::F_GEMM_NARROW;
             hipLaunchKernelGGL(dpkg::gemm_narrow, dim3((unsigned)((M + 3) / 4)), dim3(256), (size_t)K * Nn * 4, st, a, K,
                                W + w, W + b, c, ldc, M, Nn, K, mode, tpl, tps, J);
             return;
@@ -791,6 +828,7 @@ static void gen_forward(GenModel* g, hipStream_t st, const float* x, int N, cons
         if (pk && vec && sk && ldc % 4 == 0 && al16(c) && al16(W + b) && (!tpl || (al16(tpl) && tps % 4 == 0)) &&
             (size_t)M * K * 4 + (size_t)K * 4 < dpkg::SK_OOR) {
             const dim3 gs((unsigned)((M + 15) / 16), (unsigned)(((Nn + 15) / 16 + pk->NJ - 1) / pk->NJ));
+            g->forms |= pk->NJ == 4 ? dpkg::F_GEMM_SK4 : dpkg::F_GEMM_SK2;
             if (pk->NJ == 4)
                 hipLaunchKernelGGL(dpkg::gemm_sk<4>, gs, dim3(256), 0, st, a, K, g->devp + pk->off, W + b, c, ldc, M, Nn,
                                    K, mode, tpl, tps, J);
@@ -801,12 +839,15 @@ static void gen_forward(GenModel* g, hipStream_t st, const float* x, int N, cons
         }
 #define DPKG_GEMM(BM_, V_) hipLaunchKernelGGL((dpkg::gemm<BM_, V_>), grid, dim3(256), 0, st, a, K, W + w, W + b, c, ldc, M, Nn, K, mode, tpl, tps, J)
         if (bm == 128) {
+            g->forms |= vec ? dpkg::F_GEMM_128_VEC : dpkg::F_GEMM_128_SCALAR;
             if (vec) DPKG_GEMM(128, true);
             else DPKG_GEMM(128, false);
         } else if (bm == 64) {
+            g->forms |= vec ? dpkg::F_GEMM_64_VEC : dpkg::F_GEMM_64_SCALAR;
             if (vec) DPKG_GEMM(64, true);
             else DPKG_GEMM(64, false);
         } else {
+            g->forms |= vec ? dpkg::F_GEMM_32_VEC : dpkg::F_GEMM_32_SCALAR;
             if (vec) DPKG_GEMM(32, true);
             else DPKG_GEMM(32, false);
         }
@@ -814,6 +855,7 @@ static void gen_forward(GenModel* g, hipStream_t st, const float* x, int N, cons
     };
     auto cheb = [&](const float* xin, int C) {
         const size_t lds = ((size_t)J * C + 2 * J * J) * 4;
+        g->forms |= lds <= 65536 ? dpkg::F_CHEB_T : dpkg::F_CHEB_F;
         if (lds <= 65536)
             hipLaunchKernelGGL(dpkg::cheb_basis<true>, dim3((unsigned)N), dim3(256), lds, st, W + g->s.t1, W + g->s.t2, xin,
                                Zs, N, J, C);
@@ -823,6 +865,7 @@ static void gen_forward(GenModel* g, hipStream_t st, const float* x, int N, cons
     };
     auto graph = [&](size_t lg, const float* xin, int C, float* yout) {
         const size_t lds = ((size_t)J * C + J * J) * 4;
+        g->forms |= lds <= 65536 ? dpkg::F_GRAPH_T : dpkg::F_GRAPH_F;
         if (lds <= 65536)
             hipLaunchKernelGGL(dpkg::graph<true>, dim3((unsigned)N), dim3(256), lds, st, W + lg, xin, C, yout, C, N, J, C);
         else
@@ -837,10 +880,12 @@ static void gen_forward(GenModel* g, hipStream_t st, const float* x, int N, cons
                            W + o.n0b);
         gemm(Ys, D, o.wqkv, o.bqkv, Zs, 3 * D, 3 * D, dpkg::G_BIAS);
         // poses per workgroup: enough (head, query) threads to fill 256, within 64 KB of LDS
-        const bool avec = (D / g->s.H) % 4 == 0 && D % 8 == 0;
+        // (the vector form stores 16 bytes at a time to As: see graph on when As is not 16-byte aligned)
+        const bool avec = (D / g->s.H) % 4 == 0 && D % 8 == 0 && (reinterpret_cast<uintptr_t>(As) & 15) == 0;
         const size_t pose_bytes = (size_t)J * (3 * D + (avec ? 4 : 1)) * 4;
         const int ppb = std::max(1, std::min(256 / (g->s.H * J), (int)(65536 / pose_bytes)));
         const unsigned ab = (unsigned)((N + ppb - 1) / ppb);
+        g->forms |= pose_bytes > 65536 ? dpkg::F_ATTENTION_FF : avec ? dpkg::F_ATTENTION_TT : dpkg::F_ATTENTION_TF;
         if (pose_bytes > 65536)
             hipLaunchKernelGGL((dpkg::attention<false, false>), dim3((unsigned)N), dim3(256), 0, st, Zs, As, N, J, D,
                                g->s.H, mask, pmask, 1);

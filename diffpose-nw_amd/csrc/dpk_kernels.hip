@@ -817,6 +817,10 @@ int dpk_create(const dpk_config* cfg, dpk_handle** out) {
     if (pose_io) kind = 1;
     else if (cfg->coords_in == cfg->coords_out) kind = 0;
     else return DPK_E_UNSUPPORTED;
+    // GCNdiff's timestep embedding spreads hid_dim / 2 frequencies over log(10000) / (hid_dim / 2 - 1)
+    // (models/gcndiff.py:15-33): hid_dim 2 and 3 divide by zero there (the reference raises ZeroDivisionError;
+    // gen_temb would hand out NaN).  GCNpose never evaluates the embedding.
+    if (kind == 0 && cfg->hid_dim < 4) return DPK_E_UNSUPPORTED;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || cfg->device < 0 || cfg->device >= ndev) return DPK_E_HIP;
     dpk_handle* h = new dpk_handle();
@@ -1229,6 +1233,12 @@ int dpk_debug_resources(dpk_handle* h, int* out, int n) {
                       sched_tps(h) ? (int)(spare / h->w.inst->tp) : 0, gen_graph_count(h->gen),
                       sched_tps(h) ? 0 : (int)((spare * 4) >> 10)};
     for (int i = 0; i < n && i < 8; ++i) out[i] = v[i];
+    return DPK_OK;
+}
+
+int dpk_debug_generic_forms(dpk_handle* h, unsigned* forms) {
+    if (!h || !forms) return DPK_E_INVALID;
+    *forms = gen_take_forms(h->gen);
     return DPK_OK;
 }
 

@@ -68,6 +68,9 @@ class _HipModel:
         cfg = _lib.DpkConfig(hid, nl, nh, npts, coords[0], coords[1], self.device.index)
         h = ctypes.c_void_p()
         rc = L.dpk_create(ctypes.byref(cfg), ctypes.byref(h))
+        if rc == -2 and self.KIND == "diff" and hid < 4:      # no handle holds the text of a refused create
+            raise _lib.DpkError("dpk_create", rc, f"GCNdiff needs hid_dim >= 4, got {hid}: its timestep embedding "
+                                                  "divides by hid_dim // 2 - 1 (models/gcndiff.py:15-33)")
         _lib.check(None, "dpk_create", rc)
         self._h = h
         self.n_pts = npts
@@ -242,6 +245,18 @@ class _HipModel:
         keys = ("captures", "tracked", "released", "free_slots", "retired_schedules", "eps_spare_poses",
                 "generic_loop_graphs", "generic_spare_kib")
         return dict(zip(keys, list(buf)))
+
+    # bit i of dpk_debug_generic_forms (csrc/dpk_generic.inc, dpkg::GenForm)
+    GENERIC_FORMS = ("gemm_narrow", "gemm_sk<4>", "gemm_sk<2>", "gemm<128,vec>", "gemm<128,scalar>", "gemm<64,vec>",
+                     "gemm<64,scalar>", "gemm<32,vec>", "gemm<32,scalar>", "attention<TT>", "attention<TF>",
+                     "attention<FF>", "graph<T>", "graph<F>", "cheb_basis<T>", "cheb_basis<F>")
+
+    def debug_generic_forms(self) -> set:
+        """Test hook (dpk_debug_generic_forms): the names of the per-op kernel forms this model's calls have
+        launched (or recorded into a loop graph) since the last read; empty on a persistent-sampler handle."""
+        w = ctypes.c_uint(0)
+        _lib.check(self._h, "dpk_debug_generic_forms", _lib.lib().dpk_debug_generic_forms(self._h, ctypes.byref(w)))
+        return {name for i, name in enumerate(self.GENERIC_FORMS) if (w.value >> i) & 1}
 
     def profile(self, enable: bool = True) -> None:
         """Bracket each model-kernel launch with HIP events (see dpk_profile)."""

@@ -81,8 +81,10 @@ int dpk_version(void);
 /* Create a handle on cfg->device.  Replaces GCNdiff(adj, config) construction
  * (models/gcndiff.py:55-99; runners/diffpose_frame.py:118-127).  The shape every reference config
  * uses (hid_dim 96, n_head 4, n_pts 17, num_layer 1..5, coords [5,5] or GCNpose's [2,3]) runs the
- * persistent sampler; any other shape with hid_dim a multiple of n_head, n_pts <= 32 and coords
- * in == out (or [2,3]) runs the generic-shape path: the same model as per-op HIP kernels, or, for GCNdiff
+ * persistent sampler; any other shape with hid_dim a multiple of n_head (and, for GCNdiff, at least 4:
+ * its timestep embedding divides by hid_dim / 2 - 1, models/gcndiff.py:15-33, where the reference raises
+ * ZeroDivisionError for hid_dim 2 and 3; GCNpose has no embedding and takes hid_dim >= 2), 2 <= n_pts <= 32
+ * and coords in == out (or [2,3]) runs the generic-shape path: the same model as per-op HIP kernels, or, for GCNdiff
  * at hid_dim 128 / n_head 8 or 4 and hid_dim 64 / n_head 2 or 4 on 17 joints (num_layer <= 5, coords [5,5]), the
  * persistent sampler compiled at that width (round 5).  The four width instances run gemm modes 0 (fp32) and
  * 1 (f16x3), the per-op kernels mode 0 alone; a call in a mode the handle's path lacks fails with
@@ -287,9 +289,17 @@ int dpk_profile_read(dpk_handle* h, float* ms_out, int cap, int* count);
  * dpk_debug_resources: out[0..7] = captures holding resources, captures whose graph holds our
  * user object, captures released (graph gone, not yet recycled), free flag slots, retired
  * schedules, spare dpk_eps capacity (poses); generic-shape handles also: K-step loops recorded as
- * hipGraphs (out[6]) and the spare capture scratch in KiB (out[7]). */
+ * hipGraphs (out[6]) and the spare capture scratch in KiB (out[7]).
+ * dpk_debug_generic_forms: which kernel forms of the per-op path (csrc/dpk_generic.inc) the handle's calls
+ * have launched since the last read, then cleared: *forms = an OR of one bit per form the host chooses
+ * between per call, from the shape, the batch and pointer alignment (dpkg::GenForm; bit 0 gemm_narrow,
+ * 1 gemm_sk<4>, 2 gemm_sk<2>, 3..8 gemm<128|64|32> with 16-byte / scalar loads, 9..11 attention staged
+ * + vector / staged + scalar / unstaged, 12..13 graph staged / unstaged, 14..15 cheb_basis staged /
+ * unstaged).  Host bookkeeping only: it waits for nothing, and a K-step loop recorded as a hipGraph sets
+ * its bits when it is recorded, not when it is replayed.  0 on a handle that runs a persistent sampler. */
 int dpk_debug_split(dpk_handle* h, int mode, int* fallbacks);
 int dpk_debug_resources(dpk_handle* h, int* out, int n);
+int dpk_debug_generic_forms(dpk_handle* h, unsigned* forms);
 
 /* Poses per workgroup of the sampler kernel and its static LDS bytes (for docs/bench). */
 int dpk_kernel_geometry(int* poses_per_workgroup, int* threads_per_workgroup, int* lds_bytes);
