@@ -18,7 +18,9 @@ g = max|o32 - o64| computed here on the CPU,
 Each delta goes through conftest.record_delta (tag regimes/<shape>/<mode>/<regime>/<tensor>) and is
 printed with delta / g; profiles/input_regimes_deltas.jsonl keeps a run.
 
-bf16 is left out: its bar is a tolerance study of its own (tests/test_gpu_bf16_tolerance.py).
+bf16 is left out here: it is no fp32-accurate mode.  tests/test_gpu_bf16_scheme.py holds it to a restatement of
+its own arithmetic on the regimes where such a bar exists (baseline, zeros, joints_equal), and
+tests/test_gpu_bf16_tolerance.py keeps the 5-layer tolerance study.
 The f16x3 mode skips the x1000 inputs: its GEMM inputs are documented below 65504
 (include/diffpose_kernels.h, dpk_set_gemm_mode).
 """
