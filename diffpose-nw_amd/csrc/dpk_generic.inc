@@ -610,6 +610,19 @@ __global__ void __launch_bounds__(256) ddim(const float* xt, const float* __rest
     if (x0o) x0o[i] = x0;
 }
 
+// Hypothesis start x_T = x*sa + (e*scale)*sb (runners/diffpose_frame.py:359-363) for n = N * pe elements, the
+// fused kernel's arithmetic and draws (dpk::qsample_at); xT2 (null or a second copy, the trajectory's xs[0])
+__global__ void __launch_bounds__(256) qsample(const float* x, float* xT, float* xT2, long long n, int pe, float sa, float sb,
+                                               const float* __restrict__ scale, int rows,
+                                               const float* __restrict__ noise, unsigned long long seed) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int pose = (int)(i / pe);
+    const float v = dpk::qsample_at(x[i], pose, (int)(i - (long long)pose * pe), pe, sa, sb, scale, rows, noise, seed);
+    xT[i] = v;
+    if (xT2) xT2[i] = v;
+}
+
 // GCNpose's uvxyz assembly (runners/diffpose_frame.py:337-342) and xyz output, as dpk_pose's
 __global__ void __launch_bounds__(256) pose_out(const float* __restrict__ x2d, const float* __restrict__ y, int N,
                                                 int J, int cin, int cout, float* __restrict__ xyz,
@@ -922,12 +935,20 @@ static void gen_temb(GenModel* g, hipStream_t st, const float* tvals, int tstrid
                        W + g->s.d1b, W + g->s.wtp, W + g->s.btp, tvals, tstride, g->s.D, g->s.E, g->s.L, neg, tproj);
 }
 
+// One dpkg::qsample launch over N poses of pe floats (dpk_q_sample, and gen_sample's copy-in with the start on)
+static void gen_qsample(hipStream_t st, const float* x, float* xT, float* xT2, int N, int pe, const StartSpec& s,
+                        uint64_t seed) {
+    const long long n = (long long)N * pe;
+    hipLaunchKernelGGL(dpkg::qsample, dim3(gen_blocks(n)), dim3(256), 0, st, x, xT, xT2, n, pe, s.sa, s.sb, s.scale,
+                       s.rows, s.noise, (unsigned long long)seed);
+}
+
 // dpk_sample on the generic path: one forward + DDIM update per step.  Without trajectory outputs or
 // caller noise the loop is the recorded hipGraph over the state buffer xt in the scratch (x copied in,
 // the final copied out); otherwise the launches go straight to the caller's stream, the state in `out`.
 // DPK_GEN_GRAPH=0 turns the graph off (A/B).
 static int gen_sample(dpk_handle* h, Sched* sc, const float* x, float* out, float* xs, float* x0s, int N,
-                      uint64_t seed, const float* noise, hipStream_t st, bool cap) {
+                      uint64_t seed, const float* noise, const StartSpec* start, hipStream_t st, bool cap) {
     GenModel* g = h->gen;
     const int K = sc->K;
     const long long n = (long long)N * g->s.J * g->s.cin;
@@ -994,13 +1015,19 @@ static int gen_sample(dpk_handle* h, Sched* sc, const float* x, float* out, floa
         }
     }
     rc = profiled(h, st, cap, "dpk_sample", [&]() -> int {
-        if (xs) HIPCHK(h, hipMemcpyAsync(xs, x, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+        // the loop's state starts as x, or with the hypothesis start on as x_T (then xs[0] too): outside the
+        // recorded loop either way
+        float* state = graphed ? xt : out;
+        if (start) {
+            gen_qsample(st, x, state, xs, N, g->s.J * g->s.cin, *start, seed);
+        } else {
+            if (xs) HIPCHK(h, hipMemcpyAsync(xs, x, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+            HIPCHK(h, hipMemcpyAsync(state, x, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+        }
         if (graphed) {
-            HIPCHK(h, hipMemcpyAsync(xt, x, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
             HIPCHK(h, hipGraphLaunch(ex, st));
             HIPCHK(h, hipMemcpyAsync(out, xt, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
         } else {
-            HIPCHK(h, hipMemcpyAsync(out, x, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
             body(st, out);
         }
         HIPCHK(h, hipGetLastError());

@@ -20,29 +20,39 @@ static void fused_temb(const float* temb, const float* t, int stride, int count,
 // One sample_kernel launch of `blocks` workgroups for the graph pattern (sparse: the compiled H36M one),
 // the noise source (the caller's draws, ZM = 1, or counter-based) and the GEMM mode gm (0 fp32 from W;
 // 1 f16x3 / 2 bf16 from W16: each compiled where the instance's descriptor has the mode, SHAPE.modes; a mode it
-// lacks never gets here, check_ready refuses it).
-template <int MODE, bool SP, int ZM>
+// lacks never gets here, check_ready refuses it).  ST: the hypothesis start (dpk_sample_start, M_SAMPLE only).
+template <int MODE, bool SP, int ZM, bool ST = false>
 static void launch_gemm_mode(int gm, dim3 grid, size_t shmem, hipStream_t st, const SampleArgs& a, const float* W,
                              const char* W16) {
     if constexpr (SHAPE.has_mode(1)) {
         if (gm == 1) {
-            hipLaunchKernelGGL((sample_kernel<MODE, SP, 1, ZM>), grid, dim3(NT), shmem, st, a, W, W16);
+            hipLaunchKernelGGL((sample_kernel<MODE, SP, 1, ZM, ST>), grid, dim3(NT), shmem, st, a, W, W16);
             return;
         }
     }
     if constexpr (SHAPE.has_mode(2)) {
         if (gm == 2) {
-            hipLaunchKernelGGL((sample_kernel<MODE, SP, 2, ZM>), grid, dim3(NT), shmem, st, a, W, W16);
+            hipLaunchKernelGGL((sample_kernel<MODE, SP, 2, ZM, ST>), grid, dim3(NT), shmem, st, a, W, W16);
             return;
         }
     }
-    hipLaunchKernelGGL((sample_kernel<MODE, SP, 0, ZM>), grid, dim3(NT), shmem, st, a, W, W16);
+    hipLaunchKernelGGL((sample_kernel<MODE, SP, 0, ZM, ST>), grid, dim3(NT), shmem, st, a, W, W16);
 }
 template <int MODE>
 static void launch_sample(bool sparse, int gm, int blocks, size_t shmem, hipStream_t st, const SampleArgs& a,
                           const float* W, const char* W16) {
     const dim3 grid((unsigned)blocks);
     if constexpr (MODE == M_SAMPLE) {
+        if (a.start_on) {
+            if (a.noise) {
+                if (sparse) launch_gemm_mode<MODE, true, 1, true>(gm, grid, shmem, st, a, W, W16);
+                else launch_gemm_mode<MODE, false, 1, true>(gm, grid, shmem, st, a, W, W16);
+            } else {
+                if (sparse) launch_gemm_mode<MODE, true, 0, true>(gm, grid, shmem, st, a, W, W16);
+                else launch_gemm_mode<MODE, false, 0, true>(gm, grid, shmem, st, a, W, W16);
+            }
+            return;
+        }
         if (a.noise) {
             if (sparse) launch_gemm_mode<MODE, true, 1>(gm, grid, shmem, st, a, W, W16);
             else launch_gemm_mode<MODE, false, 1>(gm, grid, shmem, st, a, W, W16);

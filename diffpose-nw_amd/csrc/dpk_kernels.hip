@@ -102,6 +102,15 @@ struct SampleArgs {
     const float* noise;   // [K][N][17][5] caller noise for c1*z (the reference's per-step randn_like), or null
     int* split_stats;     // device counter: second halves that recomputed their first half's steps
     int split_dbg;        // dpk_debug_split: 0 normal; 1 first halves start late; 2 no idle wait
+    // Hypothesis start (dpk_sample_start; after the round-4 fields for the same reason): with start_on the
+    // launch runs the START instantiation of the kernel, whose load of x_in gives
+    // x_T = x*start_sa + (e*scale)*start_sb (qsample_elem) and writes it to xs[0]
+    int start_on;
+    float start_sa;       // sqrtf(alpha_bar[t_start + 1])
+    float start_sb;       // sqrtf(1 - alpha_bar[t_start + 1])
+    const float* start_scale;   // [start_scale_rows][17][5], pose n reads row n % start_scale_rows; null: ones
+    int start_scale_rows;
+    const float* start_noise;   // [N][17][5] the caller's draws e, or null: normal_noise(seed, -1, element)
 #if DPK_TRACE
     unsigned long long* trace;   // [blocks][NW][TRACE_SLOTS]
     int trace_step;
@@ -291,6 +300,7 @@ struct dpk_handle {
     hipStream_t aux = nullptr;     // handle-internal stream for schedule construction
     uint64_t weights_gen = 0;      // bumped by every weight/graph upload
     Sched* sched = nullptr;        // current schedule
+    std::vector<float> abar;       // the alpha_bar table of the last dpk_set_schedule (the hypothesis start's a)
     std::vector<Sched*> retired;   // replaced schedules not yet known to be unused
     ScratchPool pool;              // timestep projections of dpk_eps (and dpk_sample, !sched_tps) or per-op scratch
     Stage stage;                   // host staging of the weights and the graph, whatever the shape
@@ -707,6 +717,14 @@ static SampleArgs sample_args(const dpk_handle* h, const float* arena, const flo
     a.noise = noise;
     return a;
 }
+// The hypothesis start of one dpk_sample_start / dpk_q_sample call (start_spec): the two scalars of
+// alpha_bar[t_start + 1], the scale rows and the caller's draws (null: counter-based)
+struct StartSpec {
+    float sa, sb;
+    const float* scale;
+    int rows;
+    const float* noise;
+};
 static SampleArgs pose_args(const dpk_handle* h, const float* arena, const float* zeros, const float* x2d, float* xyz,
                             float* uvxyz, int N, int H, int root_mode) {
     SampleArgs a = eps_args(h, arena, zeros, x2d, xyz, N);
@@ -796,7 +814,7 @@ static int enter_call(dpk_handle* h, int N, const char* who, hipStream_t st, boo
 
 extern "C" {
 
-int dpk_version(void) { return 100; }
+int dpk_version(void) { return 101; }
 
 int dpk_kernel_geometry(int* ppw, int* tpw, int* lds) {
     if (ppw) *ppw = P;
@@ -989,6 +1007,7 @@ int dpk_set_schedule(dpk_handle* h, const float* abar, int n_alpha, const int* s
     }
     HIPCHK(h, hipSetDevice(h->device));
     sched_sweep(h);
+    h->abar.assign(abar, abar + n_alpha);
     // an identical schedule keeps its device buffers (and every graph captured with them)
     if (h->sched && h->sched->K == K && h->sched->eta == eta && h->sched->h_coef == c) return DPK_OK;
     Sched* s = new Sched();
@@ -1073,12 +1092,40 @@ int dpk_sample(dpk_handle* h, const float* x, float* out, float* xs, float* x0s,
     return dpk_sample_noise(h, x, out, xs, x0s, N, seed, nullptr, stream);
 }
 
+// The scalars of a hypothesis start at t_start from the handle's alpha_bar table, fp32 like the reference's
+// a.sqrt() and (1.0 - a).sqrt() (runners/diffpose_frame.py:363)
+static int start_spec(dpk_handle* h, const char* who, int N, int t_start, const float* scale, int scale_rows,
+                      const float* start_noise, StartSpec* s) {
+    if (h->abar.empty() || !h->sched) return fail(h, DPK_E_INVALID, std::string(who) + ": no schedule set (dpk_set_schedule)");
+    if ((size_t)t_start + 1 >= h->abar.size())
+        return fail(h, DPK_E_INVALID, std::string(who) + ": t_start " + std::to_string(t_start) + " outside the alpha table (index t_start + 1 of " +
+                                          std::to_string(h->abar.size()) + " entries)");
+    if (scale && (scale_rows < 1 || N % scale_rows != 0))
+        return fail(h, DPK_E_INVALID, std::string(who) + ": scale_rows " + std::to_string(scale_rows) + " must be at least 1 and divide N = " +
+                                          std::to_string(N));
+    const float a = h->abar[(size_t)t_start + 1], one = 1.0f;
+    volatile float sa = sqrtf(a);
+    volatile float om = one - a;
+    volatile float sb = sqrtf(om);
+    *s = StartSpec{sa, sb, scale, scale ? scale_rows : 1, start_noise};
+    return DPK_OK;
+}
+
 int dpk_sample_noise(dpk_handle* h, const float* x, float* out, float* xs, float* x0s, int N, uint64_t seed,
                      const float* noise, void* stream) {
+    return dpk_sample_start(h, x, out, xs, x0s, N, seed, noise, -1, nullptr, 0, nullptr, stream);
+}
+
+int dpk_sample_start(dpk_handle* h, const float* x, float* out, float* xs, float* x0s, int N, uint64_t seed,
+                     const float* noise, int t_start, const float* scale, int scale_rows, const float* start_noise,
+                     void* stream) {
     if (!h) return DPK_E_INVALID;
     if (N < 0 || (N > 0 && (!x || !out))) return fail(h, DPK_E_INVALID, "dpk_sample: bad args");
     int rc = check_ready(h);
     if (rc) return rc;
+    const bool start_on = t_start >= 0;
+    StartSpec start{};
+    if (start_on && (rc = start_spec(h, "dpk_sample_start", N, t_start, scale, scale_rows, start_noise, &start))) return rc;
     Sched* sc = h->sched;
     if (!sc) return fail(h, DPK_E_STATE, "schedule not set");
     if (N == 0) return DPK_OK;
@@ -1088,14 +1135,23 @@ int dpk_sample_noise(dpk_handle* h, const float* x, float* out, float* xs, float
     bool cap = false;
     if ((rc = enter_call(h, N, "dpk_sample", st, &cap))) return rc;
     if (!cap) sched_sweep(h);
-    if (h->gen) return gen_sample(h, sc, x, out, xs, x0s, N, seed, noise, st, cap);
+    if (h->gen) return gen_sample(h, sc, x, out, xs, x0s, N, seed, noise, start_on ? &start : nullptr, st, cap);
     float* tps = sc->tps;            // per-step projections [K][NL][D]: the schedule's, or this call's
     if (!sched_tps(h)) {
         if ((rc = gen_scratch(h, st, cap, (size_t)sc->K * h->w.inst->tp, &tps, "dpk_sample"))) return rc;
         h->w.inst->temb(h->w.temb, sc->coef + 5, 6, sc->K, tps, st);
     }
-    if (xs) HIPCHK(h, hipMemcpyAsync(xs, x, (size_t)N * PE * 4, hipMemcpyDeviceToDevice, st));
+    // xs[0]: x, or with the start on x_T, which the kernel writes
+    if (xs && !start_on) HIPCHK(h, hipMemcpyAsync(xs, x, (size_t)N * PE * 4, hipMemcpyDeviceToDevice, st));
     SampleArgs a = sample_args(h, h->w.arena, tps, sc, x, out, xs, x0s, N, seed, noise);
+    if (start_on) {
+        a.start_on = 1;
+        a.start_sa = start.sa;
+        a.start_sb = start.sb;
+        a.start_scale = start.scale;
+        a.start_scale_rows = start.rows;
+        a.start_noise = start.noise;
+    }
 #if DPK_TRACE
     if (h->trace_step >= 0) {
         const size_t len = (size_t)((N + P - 1) / P) * tile_waves(h) * TRACE_SLOTS;
@@ -1111,6 +1167,24 @@ int dpk_sample_noise(dpk_handle* h, const float* x, float* out, float* xs, float
 #endif
     rc = profiled(h, st, cap, "dpk_sample", [&] { return launch_sampler(h, M_SAMPLE, st, a, cap); });
     return rc ? rc : sched_note_use(h, sc, st, cap);
+}
+
+int dpk_q_sample(dpk_handle* h, const float* x, float* xT, int N, int t_start, const float* scale, int scale_rows,
+                 const float* start_noise, uint64_t seed, void* stream) {
+    if (!h) return DPK_E_INVALID;
+    if (N < 0 || t_start < 0 || (N > 0 && (!x || !xT))) return fail(h, DPK_E_INVALID, "dpk_q_sample: bad args");
+    StartSpec start{};
+    int rc = start_spec(h, "dpk_q_sample", N, t_start, scale, scale_rows, start_noise, &start);
+    if (rc) return rc;
+    if (N == 0) return DPK_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    bool cap = false;
+    if ((rc = capturing(h, st, &cap))) return rc;
+    if (!cap) cap_sweep(h);
+    gen_qsample(st, x, xT, nullptr, N, h->gen ? h->gen->s.J * h->gen->s.cin : PE, start, seed);
+    HIPCHK(h, hipGetLastError());
+    return DPK_OK;
 }
 
 int dpk_pose(dpk_handle* h, const float* x2d, float* xyz, float* uvxyz, int N, int H, int root_mode,

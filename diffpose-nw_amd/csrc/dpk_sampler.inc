@@ -111,6 +111,23 @@ __device__ __forceinline__ void ddim_elem(const float* cf, float xt, float et, f
     xn = (cf[2] * x0 + cf[3] * z) + cf[4] * et;
 }
 
+// Hypothesis start for one element (runners/diffpose_frame.py:359-363): x_T = x*sqrt(a) + (e*noise_scale)*sqrt(1-a)
+// with a = alpha_bar[t_start + 1], fp32 in the reference's order, no contraction: four roundings.
+__device__ __forceinline__ float qsample_elem(float x, float e, float scale, float sa, float sb) {
+    return (x * sa) + ((e * scale) * sb);
+}
+// ... for element r of pose `pose` (pe floats per pose): e from the caller's [N][pe] draws or counter-based at
+// step -1 (eta's per-step draws use steps 0..K-1), keyed by the global element index alone; scale row
+// pose % rows (the reference's hypothesis-major repeat), null = ones (e * 1 is e)
+__device__ __forceinline__ float qsample_at(float x, int pose, int r, int pe, float sa, float sb,
+                                            const float* __restrict__ scale, int rows,
+                                            const float* __restrict__ noise, unsigned long long seed) {
+    const long long g = (long long)pose * pe + r;
+    const float e = noise ? noise[g] : normal_noise(seed, -1, g);
+    const float sc = scale ? scale[(size_t)(pose % rows) * pe + r] : 1.0f;
+    return qsample_elem(x, e, sc, sa, sb);
+}
+
 // DPP row (16-lane) rotations and all-reduces
 template <int J>
 __device__ __forceinline__ float row_ror(float x) {
@@ -2157,9 +2174,13 @@ __device__ __forceinline__ bool split_wait(const SampleArgs& a, int j, int tid) 
 // ---------------------------------------------------------------------------------------
 // The sampler: K DDIM steps (or one eps evaluation, or one GCNpose forward) for P poses
 // per workgroup.
-template <int MODE, bool SPARSE, int G16, int ZM = 0>
+template <int MODE, bool SPARSE, int G16, int ZM = 0, bool START = false>
 // ZM, the z of the DDIM update (sample mode): 0 counter-based draws when eta != 0, else 0; 1 the caller's
 // buffer (dpk_sample_noise).  Separate instantiations: the buffer read is not in the usual launch.
+// START (sample mode): the hypothesis start of dpk_sample_start in the tile's load of x_in.  A template flag and not
+// a launch-uniform branch on SampleArgs.start_on: the branch is a dozen instructions ahead of the step loop, yet with
+// it in the one kernel f16x3 measured 0.48 % slower than the parent build in 9 of 9 alternating pairs (fp32 equal,
+// bf16 K=100 0.41 % faster: code placement, profiles/hypothesis_start_ab.txt); START = false compiles the parent's kernel.
 // `arena` is a separate restrict kernel argument: the compiler can then prove the weight arena
 // is never written during the launch and turns its wave-uniform loads (Laplacians, Chebyshev
 // terms, LayerNorm gains, biases) into scalar s_load (in the SampleArgs struct it cannot, and
@@ -2217,16 +2238,37 @@ __global__ void __launch_bounds__(NT, 1) sample_kernel(SampleArgs a, const float
         }
     } else {
         const float* src = a.x_in;
+        bool start = false;   // block-uniform: this load is of x_in and the hypothesis start is on
         if constexpr (MODE == M_SAMPLE) {
             if (half == 1 && !split_claim(a, tile - a.split_full, tid)) return;   // the second half took it
+            start = START;
             if (half == 2) {
-                // second half of a step-split tile: x_t at step split_k from the first half, or (it never
-                // started) the whole tile from x_in
-                if (split_wait(a, tile - a.split_full, tid)) src = a.x_out;
-                else s_beg = 0;
+                // second half of a step-split tile: x_t at step split_k from the first half (the start is
+                // in it already), or (it never started) the whole tile from x_in
+                if (split_wait(a, tile - a.split_full, tid)) {
+                    src = a.x_out;
+                    start = false;
+                } else {
+                    s_beg = 0;
+                }
             }
         }
-        for (int i = tid; i < R * CIN; i += NT) XST[i] = i < nvalid ? src[(size_t)pose0 * PE + i] : 0.f;
+        if (START && start) {
+            // x_T of the tile's valid rows (padded rows stay 0); it is xs[0] of the trajectory
+            for (int i = tid; i < R * CIN; i += NT) {
+                float v = 0.f;
+                if (i < nvalid) {
+                    const int p = i / PE;
+                    const size_t g = (size_t)pose0 * PE + i;
+                    v = qsample_at(a.x_in[g], pose0 + p, i - p * PE, PE, a.start_sa, a.start_sb, a.start_scale,
+                                   a.start_scale_rows, a.start_noise, a.seed);
+                    if (a.xs) a.xs[g] = v;
+                }
+                XST[i] = v;
+            }
+        } else {
+            for (int i = tid; i < R * CIN; i += NT) XST[i] = i < nvalid ? src[(size_t)pose0 * PE + i] : 0.f;
+        }
     }
     // LayerNorm parameters of every layer, staged once per launch (the per-lane column slices
     // are not wave-uniform, and as global loads their L2 latency sat on the LN critical path)

@@ -325,15 +325,44 @@ class HipGCNdiff(_HipModel):
 
     __call__ = forward
 
+    def _check_start(self, x, t_start, start_scale, start_noise):
+        """The hypothesis-start arguments of ``sample`` / ``q_sample`` for the batch x: (t_start, scale,
+        scale rows, draws) with the tensors contiguous float32 on x's device, or None for no scale / draws."""
+        t_start = int(t_start)
+        if t_start < 0:
+            raise ValueError(f"t_start must be a timestep >= 0, got {t_start}")
+        pose = tuple(x.shape[1:])
+        rows = 0
+        if start_scale is not None:
+            if not (torch.is_tensor(start_scale) and start_scale.dtype == torch.float32 and start_scale.dim() == 3
+                    and tuple(start_scale.shape[1:]) == pose and start_scale.device == x.device):
+                raise ValueError(f"start_scale must be a float32 tensor of shape (S,) + {pose} on {x.device}")
+            start_scale = start_scale.contiguous()
+            rows = start_scale.shape[0]
+        if start_noise is not None:
+            if not (torch.is_tensor(start_noise) and start_noise.dtype == torch.float32
+                    and start_noise.shape == x.shape and start_noise.device == x.device):
+                raise ValueError(f"start_noise must be a float32 tensor of shape {tuple(x.shape)} on {x.device}")
+            start_noise = start_noise.contiguous()
+        return t_start, start_scale, rows, start_noise
+
     def sample(self, x, seq, betas, eta: float = 0.0, mask=None, seed: int = 0, trajectory: bool = False,
-               out=None, noise=None):
+               out=None, noise=None, t_start=None, start_scale=None, start_noise=None):
         """Run the whole DDIM loop on device.  Returns the final x, or (xs, x0s) stacks
         ([K+1,N,17,5], [K,N,17,5]) when ``trajectory`` is set.  ``noise``: None (counter-based
         draws from ``seed`` when eta > 0) or a [K,N,17,5] float32 device tensor whose slice k is the
         z of the k-th executed step (the reference's per-step ``torch.randn_like(x)``,
-        common/utils_diff.py:65; see ``utils_diff.draw_noise``)."""
+        common/utils_diff.py:65; see ``utils_diff.draw_noise``).
+
+        ``t_start`` (default None: start from x as given) turns the noised hypothesis start on: the loop
+        starts from ``x_T = x * a.sqrt() + (e * start_scale) * (1 - a).sqrt()`` with ``a`` the alpha-bar of
+        timestep ``t_start`` (runners/diffpose_frame.py:355-363), computed where the kernel loads x, and
+        ``xs[0]`` is x_T.  ``start_scale``: [S,17,5] with S dividing N (pose n reads row n % S: the GMM
+        sampler's un-repeated noise_scale serves hypothesis-major rows) or None (ones); ``start_noise``:
+        the draws e, [N,17,5], or None (counter-based from ``seed``, independent of batch size)."""
         x = self._check_x(x)
         self.set_schedule(seq, betas, eta)
+        start = None if t_start is None else self._check_start(x, t_start, start_scale, start_noise)
         if noise is not None:
             shape = (self.K,) + tuple(x.shape)
             if not (torch.is_tensor(noise) and noise.is_cuda and noise.dtype == torch.float32
@@ -354,7 +383,13 @@ class HipGCNdiff(_HipModel):
         xs_p = xs.data_ptr() if xs is not None else None
         x0s_p = x0s.data_ptr() if x0s is not None else None
         seed_c = ctypes.c_uint64(seed & (2**64 - 1))
-        if noise is None:
+        if start is not None:
+            t0, sc, rows, e = start
+            rc = L.dpk_sample_start(self._h, x.data_ptr(), out.data_ptr(), xs_p, x0s_p, n, seed_c,
+                                    noise.data_ptr() if noise is not None else None, t0,
+                                    sc.data_ptr() if sc is not None else None, rows,
+                                    e.data_ptr() if e is not None else None, stream)
+        elif noise is None:
             rc = L.dpk_sample(self._h, x.data_ptr(), out.data_ptr(), xs_p, x0s_p, n, seed_c, stream)
         else:
             rc = L.dpk_sample_noise(self._h, x.data_ptr(), out.data_ptr(), xs_p, x0s_p, n, seed_c,
@@ -362,6 +397,25 @@ class HipGCNdiff(_HipModel):
         _lib.check(self._h, "dpk_sample", rc)
         if trajectory:
             return xs, x0s
+        return out
+
+    def q_sample(self, x, t_start: int, start_scale=None, start_noise=None, seed: int = 0, out=None):
+        """The noised hypothesis start alone (dpk_q_sample): ``x * a.sqrt() + (e * start_scale) * (1 - a).sqrt()``
+        for the bound schedule's alpha-bar at ``t_start``, arguments as in ``sample``.  For model callables
+        whose loop runs on the host (``utils_diff.generalized_steps``)."""
+        pose = (self.n_pts, getattr(self, "coords_dim", COORDS)[0])     # a pose of this handle's shape
+        if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3
+                and tuple(x.shape[1:]) == pose):
+            raise ValueError(f"x must be a float32 CUDA(HIP) tensor of shape (N,) + {pose}")
+        x = x.contiguous()
+        t0, sc, rows, e = self._check_start(x, t_start, start_scale, start_noise)
+        out = torch.empty_like(x) if out is None else out
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        rc = _lib.lib().dpk_q_sample(self._h, x.data_ptr(), out.data_ptr(), x.shape[0], t0,
+                                     sc.data_ptr() if sc is not None else None, rows,
+                                     e.data_ptr() if e is not None else None,
+                                     ctypes.c_uint64(seed & (2**64 - 1)), stream)
+        _lib.check(self._h, "dpk_q_sample", rc)
         return out
 
     def ddim_update(self, xt, et, step: int, seed: int = 0, want_x0: bool = True, noise=None):

@@ -55,6 +55,19 @@ def pose_errors(out_uvxyz: torch.Tensor, targets: torch.Tensor, test_times: int 
     return (p1, p2, xyz) if return_xyz else (p1, p2)
 
 
+def hypothesis_errors(out_uvxyz: torch.Tensor, targets: torch.Tensor, test_times: int = 1, root_mode="quirk"):
+    """Per-hypothesis (MPJPE, P-MPJPE) in metres, float64 device tensors ``[test_times, F]``: every
+    hypothesis row of ``out_uvxyz [test_times*F,17,5]`` against its frame's target, not their mean
+    (``pose_errors``).  The same kernel on test_times*F "frames" of one hypothesis each.  Not in the
+    reference, which books the hypothesis mean alone (runners/diffpose_frame.py:377-387)."""
+    H = int(test_times)
+    if H < 1 or not torch.is_tensor(targets) or targets.dim() != 3:
+        raise ValueError(f"test_times must be >= 1 and targets (F, 17, 3), got {test_times!r}")
+    F = targets.shape[0]
+    p1, p2 = pose_errors(out_uvxyz, targets.repeat(H, 1, 1), 1, root_mode)
+    return p1.view(H, F), p2.view(H, F)
+
+
 class AverageMeter:
     """common/utils.py:9-24 (sum += val * n)."""
 

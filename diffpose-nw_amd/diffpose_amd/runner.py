@@ -22,6 +22,15 @@ noise source ("torch") draws the reference's randn_like sequence for the whole b
 (``runners/diffpose_frame.py:359``, then one draw per step at ``common/utils_diff.py:65``) and each
 rank keeps its rows, so the samples do not depend on the world size either.
 
+``args.noise_start`` (default False, the reference as it stands) switches the reference's commented-out
+line back on (``runners/diffpose_frame.py:355-363``): the sampler starts every hypothesis row from
+``x * a.sqrt() + (e * noise_scale) * (1 - a).sqrt()`` with ``a`` the alpha-bar of ``args.t_start`` (default
+``config.testing.test_num_diffusion_timesteps``, as ``:355``), inside the sampler launch.  A batch may then
+be a 4-tuple whose last element is the GMM sampler's ``noise_scale [B,17,5]`` (absent: ones), the ``:359``
+draw ``e`` is kept instead of dropped (drawn for the whole batch first, at eta = 0 too), and the best-of-H
+and per-hypothesis-mean MPJPE / P-MPJPE are kept in ``hypothesis_loss`` beside the reference's
+mean-aggregate (p1, p2), which stays what ``test_hyber`` returns.
+
 The H36M ``.npz`` datasets are absent offline. ``test_hyber`` therefore takes an iterable of
 ``(input_2d [B,17,2], targets_3d [B,17,3], actions [B])`` batches, the shape the reference's
 ``PoseGenerator_gmm`` loader delivers after its GMM draw. If none is given, it uses seeded
@@ -88,6 +97,9 @@ class Diffpose:
         self.inference_times, self.memory_usage = [], []
         self.diffusion_step_count = []
         self.model_diff = self.model_pose = None
+        self.noise_start = bool(getattr(args, "noise_start", False))
+        self.t_start = int(getattr(args, "t_start", config.testing.test_num_diffusion_timesteps))
+        self.hypothesis_loss = None
 
     def _adj(self):
         return adj_mx_from_edges()        # the runner's 16 H36M edges (diffpose_frame.py:120-125)
@@ -142,10 +154,30 @@ class Diffpose:
             return z
         return z[:, shard_rows(n_frames, H, world, rank).to(z.device)].contiguous()
 
-    def _frame_errors(self, input_2d, targets_3d, H, seq, i, noise, root_mode):
+    def _batch_noise_start(self, n_frames: int, H: int, K: int, world: int, rank: int):
+        """``_batch_noise`` with the hypothesis start on: (z rows or None, e rows or None).  The ``:359``
+        draw e is kept, and is drawn first for the whole batch whatever eta is (the reference draws it at
+        eta = 0 too); None for the "philox" source (the kernel's counter-based draws, keyed by the rank's
+        own row index)."""
+        from .utils_diff import draw_noise
+
+        src = getattr(self.args, "noise", "torch")
+        if src in (None, "philox"):
+            return None, None
+        full = torch.empty((H * n_frames, 17, 5), dtype=torch.float32, device=self.device)
+        e = draw_noise(full, 1, src)[0]
+        z = draw_noise(full, K, src) if float(self.args.eta) != 0.0 else None
+        if world > 1:
+            rows = shard_rows(n_frames, H, world, rank).to(e.device)
+            e = e[rows].contiguous()
+            z = None if z is None else z[:, rows].contiguous()
+        return z, e
+
+    def _frame_errors(self, input_2d, targets_3d, H, seq, i, noise, root_mode, start=None):
         """Pose model, sampler and per-frame metrics for one (shard of a) batch: float64 device
         tensors (MPJPE, P-MPJPE) in metres, one per frame.  Also records the reference's per-batch
-        timing window under ``track_metrics``."""
+        timing window under ``track_metrics``.  ``start``: (e rows or None, noise_scale rows [F,17,5] or
+        None) of the hypothesis start, which then runs inside the sampler launch."""
         F = input_2d.shape[0]
         if F == 0:
             e = torch.empty(0, dtype=torch.float64, device=self.device)
@@ -167,8 +199,14 @@ class Diffpose:
             mem0 = torch.cuda.memory_allocated(self.device)
             t0 = time.time()
         # generalized_steps(...)[0][-1]: the final sample only (no trajectory stacks)
+        kw = {}
+        if start is not None:
+            e, scale = start
+            if scale is not None:
+                scale = torch.as_tensor(scale, dtype=torch.float32).to(self.device)
+            kw = dict(t_start=self.t_start, start_scale=scale, start_noise=e)
         out = self.model_diff.sample(x, seq, self.betas, eta=self.args.eta, mask=self.src_mask,
-                                     seed=self.args.seed + i, noise=noise)
+                                     seed=self.args.seed + i, noise=noise, **kw)
         if track:
             torch.cuda.synchronize(self.device)
             self.inference_times.append(time.time() - t0)
@@ -178,6 +216,12 @@ class Diffpose:
         if track:
             torch.cuda.synchronize(self.device)
             self.metrics_times.append(time.time() - tm)
+        if start is not None:
+            # per hypothesis, beside the mean-aggregate: sums of the best of H and of the H-average per frame
+            h1, h2 = metrics.hypothesis_errors(out, targets_3d, H, root_mode)
+            self._hyp_sums += torch.stack([h1.min(0).values.sum(), h2.min(0).values.sum(),
+                                           h1.mean(0).sum(), h2.mean(0).sum()]).cpu()
+            self._hyp_frames += F
         return p1, p2
 
     def test_hyber(self, batches=None, is_train=False, n_frames: int = 4096, frame_errors=None):
@@ -185,7 +229,8 @@ class Diffpose:
         multi-rank torch.distributed job every rank returns the whole evaluation's (p1, p2)
         (module docstring).  ``frame_errors`` replaces the per-shard compute (tests of the
         distributed accounting on CPU): ``fn(input_2d, targets_3d, H, seq, batch_index, noise,
-        root_mode) -> (p1, p2)`` for the rank's frames."""
+        root_mode) -> (p1, p2)`` for the rank's frames; with ``args.noise_start`` it is also passed
+        ``start=(e rows, noise_scale rows)`` as a keyword."""
         te = self.config.testing
         H = int(te.test_times)
         seq = self._seq()
@@ -204,8 +249,11 @@ class Diffpose:
         self.inference_times, self.memory_usage = [], []
         self.pose_times, self.metrics_times = [], []
         i = -1
+        self._hyp_sums, self._hyp_frames = torch.zeros(4, dtype=torch.float64), 0
         with torch.no_grad():
-            for i, (input_2d, targets_3d, actions) in enumerate(batches):
+            for i, batch in enumerate(batches):
+                input_2d, targets_3d, actions = batch[:3]
+                noise_scale = batch[3] if self.noise_start and len(batch) > 3 else None
                 actions = list(actions)
                 input_2d = np.asarray(input_2d, dtype=np.float32)
                 targets_3d = np.asarray(targets_3d, dtype=np.float32)
@@ -213,9 +261,19 @@ class Diffpose:
                 if targets_3d.shape[0] != B or len(actions) != B:
                     raise ValueError(f"batch {i}: {B} inputs, {targets_3d.shape[0]} targets, {len(actions)} actions")
                 lo, hi = shard_frames(B, world, rank)
-                noise = self._batch_noise(B, H, len(seq), world, rank)
+                kw = {}
+                if self.noise_start:
+                    noise, e = self._batch_noise_start(B, H, len(seq), world, rank)
+                    if noise_scale is not None:
+                        noise_scale = np.asarray(noise_scale, dtype=np.float32)
+                        if noise_scale.shape != (B, 17, 5):
+                            raise ValueError(f"batch {i}: noise_scale must be ({B}, 17, 5), got {noise_scale.shape}")
+                        noise_scale = np.ascontiguousarray(noise_scale[lo:hi])
+                    kw["start"] = (e, noise_scale)
+                else:
+                    noise = self._batch_noise(B, H, len(seq), world, rank)
                 p1, p2 = frame_errors(np.ascontiguousarray(input_2d[lo:hi]), np.ascontiguousarray(targets_3d[lo:hi]),
-                                      H, seq, i, noise, root_mode)
+                                      H, seq, i, noise, root_mode, **kw)
                 if distributed:
                     # the final MPJPE reduction: per-frame (p1, p2) of every rank, in frame order
                     both = gather_frames(torch.stack([p1, p2], dim=1).to(torch.float64), B, 1)
@@ -232,6 +290,11 @@ class Diffpose:
             self.log_performance_metrics(path)
         logging.info("sum (%d) | MPJPE: %.4f | P-MPJPE: %.4f", i + 1, epoch_p1.avg, epoch_p2.avg)
         self.epoch_loss = (epoch_p1.avg, epoch_p2.avg)
+        # this rank's frames: best-of-H and per-hypothesis-average MPJPE / P-MPJPE in mm (noise_start only)
+        self.hypothesis_loss = None
+        if self._hyp_frames:
+            b1, b2, m1, m2 = (self._hyp_sums * 1000.0 / self._hyp_frames).tolist()
+            self.hypothesis_loss = {"best": (b1, b2), "mean": (m1, m2), "frames": self._hyp_frames}
         self.action_error_sum = err
         return metrics.print_error(None, err, is_train if rank == 0 else True)   # one table per job
 

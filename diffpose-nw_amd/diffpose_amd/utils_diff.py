@@ -20,6 +20,13 @@ in execution order (``common/utils_diff.py:65``); ``noise=`` selects what z is:
   [K,N,17,5] buffer, not the reference's numbers;
 * a [K,N,17,5] tensor: slice k is step k's z.
 
+The noised hypothesis start (``t_start=``, with ``start_scale=`` and ``start_noise=``): the loop starts from
+``x_T = x * a.sqrt() + (e * start_scale) * (1 - a).sqrt()``, ``a`` the alpha-bar of timestep ``t_start`` —
+the line the reference's ``test_hyber`` leaves commented out (``runners/diffpose_frame.py:355-363``).
+``start_noise`` names the source of ``e`` like ``noise``: ``"torch"`` (default, the reference's
+``torch.randn_like(input_uvxyz)`` of ``:359``, drawn before the per-step draws), ``"torch-cpu"``,
+``"philox"`` (counter-based, in the kernel) or an x-shaped tensor.  ``xs[0]`` is then the new x_T tensor.
+
 At eta = 0 the noise term is 0·z and nothing is drawn unless ``noise`` asks for it (the reference
 still advances torch's RNG by K draws there; ``noise="torch"`` reproduces that too).
 """
@@ -73,18 +80,29 @@ def generalized_steps(x, src_mask, seq, model, b, **kwargs):
     eta = float(kwargs.get("eta", 0))
     seed = int(kwargs.get("seed", 0))
     seq = [int(s) for s in seq]
+    t_start = kwargs.get("t_start")
     with torch.no_grad():
+        start = {}
+        if t_start is not None:
+            # :359's e before the per-step draws, in the reference's order
+            src = kwargs.get("start_noise", "torch")
+            if torch.is_tensor(src) and src.shape == x.shape:
+                src = src.unsqueeze(0)
+            e = draw_noise(x, 1, src, kwargs.get("generator"))
+            start = dict(t_start=int(t_start), start_scale=kwargs.get("start_scale"),
+                         start_noise=None if e is None else e[0])
         noise = draw_noise(x, len(seq), kwargs.get("noise", "torch" if eta != 0 else None), kwargs.get("generator"))
         if isinstance(model, HipGCNdiff):
-            xs_t, x0s_t = model.sample(x, seq, b, eta=eta, mask=src_mask, seed=seed, trajectory=True, noise=noise)
-            return [x] + [xs_t[k] for k in range(1, xs_t.shape[0])], [x0s_t[k] for k in range(x0s_t.shape[0])]
+            xs_t, x0s_t = model.sample(x, seq, b, eta=eta, mask=src_mask, seed=seed, trajectory=True, noise=noise,
+                                      **start)
+            return [xs_t[0] if start else x] + [xs_t[k] for k in range(1, xs_t.shape[0])], [x0s_t[k] for k in range(x0s_t.shape[0])]
         # generic callable: host loop, HIP DDIM update
         upd = kwargs.get("updater")
         if upd is None:
             upd = schedule_handle(x.device)
         upd.set_schedule(seq, b, eta)
         n = x.size(0)
-        xs, x0s = [x], []
+        xs, x0s = [upd.q_sample(x, seed=seed, **start) if start else x], []
         for step, (i, _j) in enumerate(step_pairs(seq)):
             t = torch.full((n,), float(i), device=x.device)
             et = model(xs[-1], src_mask, t, 0)

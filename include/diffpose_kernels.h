@@ -23,8 +23,8 @@
  *     that used it has passed its last launch.  Uncaptured dpk_eps calls keep their per-pose
  *     timestep projections in a buffer per caller stream.  dpk_load_weights / dpk_set_graph
  *     wait for the device to drain before overwriting the weights (configuration calls).
- *   - Graph capture (hipStreamBeginCapture / torch.cuda.graph): dpk_sample, dpk_eps, dpk_pose
- *     and dpk_ddim_update may be captured.  A captured launch reads the schedule current at
+ *   - Graph capture (hipStreamBeginCapture / torch.cuda.graph): dpk_sample (dpk_sample_noise,
+ *     dpk_sample_start), dpk_eps, dpk_pose, dpk_ddim_update and dpk_q_sample may be captured.  A captured launch reads the schedule current at
  *     capture time for the graph's whole life (a later dpk_set_schedule builds a new one and
  *     leaves the captured one in place); weights reloaded later are seen by replays.  It also
  *     keeps the key mask it was captured with: the dpk_set_mask bits by value, and the
@@ -140,7 +140,7 @@ int dpk_eps(dpk_handle* h, const float* x_dev, const float* t_dev, float* eps_de
  * persistent kernel (the per-step timestep projections come with the schedule).
  *   x_dev   [N,17,5] input x (= xs[0])
  *   out_dev [N,17,5] final sample xs[-1]
- *   xs_dev  [K+1,N,17,5] or NULL: full trajectory xs (xs[0] copied from x_dev)
+ *   xs_dev  [K+1,N,17,5] or NULL: full trajectory xs (xs[0] copied from x_dev; x_T under dpk_sample_start)
  *   x0s_dev [K,N,17,5]   or NULL: x0_preds
  *   seed: noise stream for eta > 0 (counter-based, not torch.randn_like). */
 int dpk_sample(dpk_handle* h, const float* x_dev, float* out_dev, float* xs_dev, float* x0s_dev,
@@ -153,6 +153,38 @@ int dpk_sample(dpk_handle* h, const float* x_dev, float* out_dev, float* xs_dev,
  * noise from `seed` (dpk_sample).  Read asynchronously on `stream`. */
 int dpk_sample_noise(dpk_handle* h, const float* x_dev, float* out_dev, float* xs_dev, float* x0s_dev,
                      int N, uint64_t seed, const float* noise_dev, void* stream);
+
+/* dpk_sample_noise from a noised hypothesis start: what test_hyber's commented-out line
+ * (runners/diffpose_frame.py:355-363) computes in front of generalized_steps, inside the same launch:
+ *   x_T = (x * sqrt(a)) + ((e * scale) * sqrt(1 - a)),  a = alpha_bar[t_start + 1]
+ * from the table of the last dpk_set_schedule (the reference's (1-b).cumprod(0).index_select(0, t) at
+ * t = t_start); sqrt(a) and sqrt(1 - a) are taken on the host in fp32 and every element is four fp32
+ * roundings in that order (no FMA), so x_T is bitwise what torch computes for the same inputs.  The K steps
+ * then run from x_T, and with xs_dev given xs[0] is x_T (written by the kernel; x_dev is not modified).
+ *   t_start          < 0: no start; the call is dpk_sample_noise and the four arguments below are ignored
+ *   scale_dev        [scale_rows,17,5] fp32 device or NULL (all ones).  Pose n reads row n % scale_rows, so
+ *                    the [F,17,5] noise_scale of dpk_gmm_sample serves N = H*F hypothesis-major poses (the
+ *                    reference's noise_scale.repeat(test_times,1,1)); scale_rows must divide N
+ *   start_noise_dev  [N,17,5] fp32 device: the draws e (the reference's torch.randn_like(input_uvxyz), :359),
+ *                    or NULL: counter-based draws from `seed` at step -1, a counter domain disjoint from
+ *                    eta's per-step draws (steps 0..K-1).  A pose's draw depends on the seed and its global
+ *                    element index alone, not on tiles, tail plans or N
+ * DPK_E_INVALID (with dpk_last_error text) when t_start + 1 >= n_alpha (the reference's index_select raises),
+ * when scale_rows < 1 or does not divide N, or when no schedule is set.  Capture-safe like dpk_sample: nothing
+ * is allocated, the scalars are captured by value and the pointers are read at replay.  No fixture of the
+ * reference pins this path (its :363 never executes); the yardstick is the oracle's loop started from the x_T
+ * that line gives in torch. */
+int dpk_sample_start(dpk_handle* h, const float* x_dev, float* out_dev, float* xs_dev, float* x0s_dev,
+                     int N, uint64_t seed, const float* noise_dev,
+                     int t_start, const float* scale_dev, int scale_rows, const float* start_noise_dev,
+                     void* stream);
+
+/* The start alone, x_T into xT_dev [N,17,5] (may be x_dev), for generic model callables whose loop runs on the
+ * host: the sibling of dpk_ddim_update.  Arguments, arithmetic, draws and refusals as in dpk_sample_start
+ * (t_start >= 0); needs a schedule (its alpha table), no weights.  On a per-op handle a pose has n_pts * coords_in floats. */
+int dpk_q_sample(dpk_handle* h, const float* x_dev, float* xT_dev, int N, int t_start,
+                 const float* scale_dev, int scale_rows, const float* start_noise_dev,
+                 uint64_t seed, void* stream);
 
 /* One DDIM update for an externally computed eps (generic model callables):
  * the per-element body of common/utils_diff.py:59-65 for schedule step `step`

@@ -25,7 +25,9 @@ def main():
     rows = []
     for f in glob.glob(os.path.join(a.prof_dir, "**", "*kernel_trace.csv"), recursive=True):
         for r in csv.DictReader(open(f)):
-            if f"sample_kernel<0, true, {gm}, 0>" in r["Kernel_Name"]:
+            # bench.py's launches: counter-based z, no hypothesis start (<0, true, G, 0, false>)
+            if f"sample_kernel<0, true, {gm}, 0, false>" in r["Kernel_Name"] or \
+                    f"sample_kernel<0, true, {gm}, 0>" in r["Kernel_Name"]:
                 rows.append((int(r["Start_Timestamp"]), (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6,
                              r["Kernel_Name"]))
     rows.sort()
