@@ -20,7 +20,7 @@
 
 namespace dpk_gmm {
 
-constexpr int J = 17;
+constexpr int JMIN = 2, JMAX = 32;   // the joint counts dpk_create accepts
 constexpr int KMAX = 64;   // components per joint accepted by the kernel
 
 // uniform double in [0, 1) with 53 random bits from a counter (seeded mode; not numpy's stream)
@@ -38,7 +38,7 @@ __device__ __forceinline__ double counter_uniform(uint64_t seed, uint64_t ctr) {
 // `.float()` at generators.py:46-50 does.
 template <typename T>
 __global__ void gmm_sample_kernel(const T* __restrict__ gmm, const T* __restrict__ poses3d, int n_src,
-                                  int kn, const int64_t* __restrict__ index, int F, const double* __restrict__ u,
+                                  int J, int kn, const int64_t* __restrict__ index, int F, const double* __restrict__ u,
                                   uint64_t seed, double atol, float* __restrict__ uvxyz,
                                   float* __restrict__ noise_scale, int* __restrict__ status) {
     const int gid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -92,30 +92,46 @@ __global__ void gmm_sample_kernel(const T* __restrict__ gmm, const T* __restrict
 }  // namespace dpk_gmm
 
 template <typename T>
-static int gmm_launch(const T* gmm_dev, const T* poses3d_dev, int n_src, int kernel_n, const int64_t* index_dev, int F,
-                      const double* u_dev, uint64_t seed, double atol, float* uvxyz_dev, float* noise_scale_dev,
+static int gmm_launch(const T* gmm_dev, const T* poses3d_dev, int n_src, int n_pts, int kernel_n, const int64_t* index_dev,
+                      int F, const double* u_dev, uint64_t seed, double atol, float* uvxyz_dev, float* noise_scale_dev,
                       int* status_dev, void* stream) {
+    if (n_pts < dpk_gmm::JMIN || n_pts > dpk_gmm::JMAX) return DPK_E_INVALID;
     if (F < 0 || n_src <= 0 || kernel_n < 1 || kernel_n > dpk_gmm::KMAX) return DPK_E_INVALID;
     if (F == 0) return DPK_OK;
     if (!gmm_dev || !poses3d_dev || !uvxyz_dev || !noise_scale_dev || !status_dev) return DPK_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(status_dev, 0, sizeof(int), st) != hipSuccess) return DPK_E_HIP;
-    const int n = F * dpk_gmm::J, nt = 256;
+    const int n = F * n_pts, nt = 256;
     hipLaunchKernelGGL(dpk_gmm::gmm_sample_kernel<T>, dim3((n + nt - 1) / nt), dim3(nt), 0, st, gmm_dev, poses3d_dev,
-                       n_src, kernel_n, index_dev, F, u_dev, seed, atol, uvxyz_dev, noise_scale_dev, status_dev);
+                       n_src, n_pts, kernel_n, index_dev, F, u_dev, seed, atol, uvxyz_dev, noise_scale_dev, status_dev);
     return hipGetLastError() == hipSuccess ? DPK_OK : DPK_E_HIP;
+}
+
+extern "C" int dpk_gmm_sample_n(const float* gmm_dev, const float* poses3d_dev, int n_src, int n_pts, int kernel_n,
+                                const int64_t* index_dev, int F, const double* u_dev, uint64_t seed, double atol,
+                                float* uvxyz_dev, float* noise_scale_dev, int* status_dev, void* stream) {
+    return gmm_launch(gmm_dev, poses3d_dev, n_src, n_pts, kernel_n, index_dev, F, u_dev, seed, atol, uvxyz_dev,
+                      noise_scale_dev, status_dev, stream);
+}
+
+extern "C" int dpk_gmm_sample_f64_n(const double* gmm_dev, const double* poses3d_dev, int n_src, int n_pts,
+                                    int kernel_n, const int64_t* index_dev, int F, const double* u_dev, uint64_t seed,
+                                    double atol, float* uvxyz_dev, float* noise_scale_dev, int* status_dev,
+                                    void* stream) {
+    return gmm_launch(gmm_dev, poses3d_dev, n_src, n_pts, kernel_n, index_dev, F, u_dev, seed, atol, uvxyz_dev,
+                      noise_scale_dev, status_dev, stream);
 }
 
 extern "C" int dpk_gmm_sample(const float* gmm_dev, const float* poses3d_dev, int n_src, int kernel_n,
                               const int64_t* index_dev, int F, const double* u_dev, uint64_t seed, double atol,
                               float* uvxyz_dev, float* noise_scale_dev, int* status_dev, void* stream) {
-    return gmm_launch(gmm_dev, poses3d_dev, n_src, kernel_n, index_dev, F, u_dev, seed, atol, uvxyz_dev,
-                      noise_scale_dev, status_dev, stream);
+    return dpk_gmm_sample_n(gmm_dev, poses3d_dev, n_src, 17, kernel_n, index_dev, F, u_dev, seed, atol, uvxyz_dev,
+                            noise_scale_dev, status_dev, stream);
 }
 
 extern "C" int dpk_gmm_sample_f64(const double* gmm_dev, const double* poses3d_dev, int n_src, int kernel_n,
                                   const int64_t* index_dev, int F, const double* u_dev, uint64_t seed, double atol,
                                   float* uvxyz_dev, float* noise_scale_dev, int* status_dev, void* stream) {
-    return gmm_launch(gmm_dev, poses3d_dev, n_src, kernel_n, index_dev, F, u_dev, seed, atol, uvxyz_dev,
-                      noise_scale_dev, status_dev, stream);
+    return dpk_gmm_sample_f64_n(gmm_dev, poses3d_dev, n_src, 17, kernel_n, index_dev, F, u_dev, seed, atol,
+                                uvxyz_dev, noise_scale_dev, status_dev, stream);
 }

@@ -22,12 +22,14 @@
 
 namespace dpk_metrics {
 
-constexpr int J = 17;
-constexpr int PE = J * 5;
+constexpr int JMIN = 2, JMAX = 32;   // the joint counts dpk_create accepts
 
 __device__ void jacobi4(double A[4][4], double V[4][4]) {
     for (int i = 0; i < 4; ++i)
         for (int j = 0; j < 4; ++j) V[i][j] = i == j ? 1.0 : 0.0;
+    // the sweep loop stays a loop; the (p, q) pairs inside are unrolled so that A and V are indexed
+    // by constants and live in registers
+#pragma unroll 1
     for (int sweep = 0; sweep < 16; ++sweep) {
         double off = 0.0, diag = 0.0;
         for (int i = 0; i < 4; ++i)
@@ -36,7 +38,9 @@ __device__ void jacobi4(double A[4][4], double V[4][4]) {
                 else diag += A[i][j] * A[i][j];
             }
         if (off <= 1e-30 * diag || off == 0.0) break;
+#pragma unroll
         for (int p = 0; p < 3; ++p)
+#pragma unroll
             for (int q = p + 1; q < 4; ++q) {
                 const double apq = A[p][q];
                 if (apq == 0.0) continue;
@@ -62,14 +66,32 @@ __device__ void jacobi4(double A[4][4], double V[4][4]) {
     }
 }
 
-// one thread per frame
+// Between the phases the fp32 values pass through an empty asm, after which the compiler no longer
+// knows them: it then converts them to fp64 again where a phase reads them, and does not keep 6 J
+// doubles alive from the first phase to the last (which does not fit the register file at 32 joints).
+template <int J>
+__device__ __forceinline__ void forget(float (&y)[J][3], float (&x)[J][3]) {
+#pragma unroll
+    for (int j = 0; j < J; ++j)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            asm volatile("" : "+v"(y[j][c]));
+            asm volatile("" : "+v"(x[j][c]));
+        }
+}
+
+// one thread per frame.  J (the joint count) is a template parameter so that a frame's prediction and
+// target stay in registers: with a run-time J the two arrays would be indexed private memory (scratch).
+template <int J>
 __global__ void __launch_bounds__(64) metrics_kernel(const float* __restrict__ out, const float* __restrict__ tgt,
                                                      int F, int H, int root_mode, double* __restrict__ p1,
                                                      double* __restrict__ p2, float* __restrict__ xyz_out) {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= F) return;
+    constexpr int PE = J * 5;
     float y[J][3], x[J][3];
     // hypothesis mean in fp32, sum over h then / H (torch.mean over dim 0, diffpose_frame.py:382)
+#pragma unroll
     for (int j = 0; j < J; ++j)
         for (int c = 0; c < 3; ++c) {
             float s = 0.f;
@@ -82,6 +104,7 @@ __global__ void __launch_bounds__(64) metrics_kernel(const float* __restrict__ o
     if (root_mode == 0) {
         for (int c = 0; c < 3; ++c) y[0][c] = x[0][c] = 0.f;
     } else if (root_mode == 1) {
+#pragma unroll
         for (int j = J - 1; j >= 0; --j)
             for (int c = 0; c < 3; ++c) {
                 y[j][c] -= y[0][c];
@@ -89,17 +112,22 @@ __global__ void __launch_bounds__(64) metrics_kernel(const float* __restrict__ o
             }
     }
     if (xyz_out)
+#pragma unroll
         for (int j = 0; j < J; ++j)
             for (int c = 0; c < 3; ++c) xyz_out[(size_t)f * J * 3 + j * 3 + c] = y[j][c];
+    forget<J>(y, x);
     // MPJPE
     double e1 = 0.0;
+#pragma unroll
     for (int j = 0; j < J; ++j) {
         const double d0 = (double)y[j][0] - x[j][0], d1 = (double)y[j][1] - x[j][1], d2 = (double)y[j][2] - x[j][2];
         e1 += sqrt(d0 * d0 + d1 * d1 + d2 * d2);
     }
     p1[f] = e1 / J;
+    forget<J>(y, x);
     // P-MPJPE
     double mx[3] = {0, 0, 0}, my[3] = {0, 0, 0};
+#pragma unroll
     for (int j = 0; j < J; ++j)
         for (int c = 0; c < 3; ++c) {
             mx[c] += x[j][c];
@@ -109,7 +137,9 @@ __global__ void __launch_bounds__(64) metrics_kernel(const float* __restrict__ o
         mx[c] /= J;
         my[c] /= J;
     }
+    forget<J>(y, x);
     double nx = 0.0, ny = 0.0;
+#pragma unroll
     for (int j = 0; j < J; ++j)
         for (int c = 0; c < 3; ++c) {
             const double a = x[j][c] - mx[c], b = y[j][c] - my[c];
@@ -118,7 +148,9 @@ __global__ void __launch_bounds__(64) metrics_kernel(const float* __restrict__ o
         }
     nx = sqrt(nx);
     ny = sqrt(ny);
+    forget<J>(y, x);
     double S[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};   // S[a][b] = sum_j Y0[j][a] X0[j][b]
+#pragma unroll
     for (int j = 0; j < J; ++j)
         for (int a = 0; a < 3; ++a)
             for (int b = 0; b < 3; ++b) S[a][b] += ((y[j][a] - my[a]) / ny) * ((x[j][b] - mx[b]) / nx);
@@ -129,11 +161,18 @@ __global__ void __launch_bounds__(64) metrics_kernel(const float* __restrict__ o
         {S[0][1] - S[1][0], S[2][0] + S[0][2], S[1][2] + S[2][1], -S[0][0] - S[1][1] + S[2][2]}};
     double V[4][4];
     jacobi4(N, V);
-    int k = 0;
-    for (int i = 1; i < 4; ++i)
-        if (N[i][i] > N[k][k]) k = i;
-    const double lam = N[k][k];
-    double q0 = V[0][k], qx = V[1][k], qy = V[2][k], qz = V[3][k];
+    // the largest eigenvalue and its eigenvector (the first of equal ones), by selects: indexing N
+    // and V with a run-time k would put both in private memory
+    double lam = N[0][0], q0 = V[0][0], qx = V[1][0], qy = V[2][0], qz = V[3][0];
+#pragma unroll
+    for (int i = 1; i < 4; ++i) {
+        const bool up = N[i][i] > lam;
+        lam = up ? N[i][i] : lam;
+        q0 = up ? V[0][i] : q0;
+        qx = up ? V[1][i] : qx;
+        qy = up ? V[2][i] : qy;
+        qz = up ? V[3][i] : qz;
+    }
     const double qn = sqrt(q0 * q0 + qx * qx + qy * qy + qz * qz);
     q0 /= qn;
     qx /= qn;
@@ -146,7 +185,9 @@ __global__ void __launch_bounds__(64) metrics_kernel(const float* __restrict__ o
     double t[3];
     for (int a = 0; a < 3; ++a)
         t[a] = mx[a] - sc * (Q[a][0] * my[0] + Q[a][1] * my[1] + Q[a][2] * my[2]);
+    forget<J>(y, x);
     double e2 = 0.0;
+#pragma unroll
     for (int j = 0; j < J; ++j) {
         double ss = 0.0;
         for (int a = 0; a < 3; ++a) {
@@ -159,14 +200,40 @@ __global__ void __launch_bounds__(64) metrics_kernel(const float* __restrict__ o
     p2[f] = e2 / J;
 }
 
+template <int J>
+static void launch(const float* out, const float* tgt, int F, int H, int root_mode, double* p1, double* p2,
+                   float* xyz, hipStream_t st) {
+    hipLaunchKernelGGL(metrics_kernel<J>, dim3((F + 63) / 64), dim3(64), 0, st, out, tgt, F, H, root_mode, p1, p2,
+                       xyz);
+}
+
 }  // namespace dpk_metrics
 
-extern "C" int dpk_pose_metrics(const float* out_uvxyz, const float* targets, int F, int H, int root_mode,
-                                double* p1, double* p2, float* xyz, void* stream) {
+extern "C" int dpk_pose_metrics_n(const float* out_uvxyz, const float* targets, int F, int H, int n_pts,
+                                  int root_mode, double* p1, double* p2, float* xyz, void* stream) {
+    if (n_pts < dpk_metrics::JMIN || n_pts > dpk_metrics::JMAX) return DPK_E_INVALID;
     if (F < 0 || H < 1 || root_mode < 0 || root_mode > 2) return DPK_E_INVALID;
     if (F == 0) return DPK_OK;
     if (!out_uvxyz || !targets || !p1 || !p2) return DPK_E_INVALID;
-    hipLaunchKernelGGL(dpk_metrics::metrics_kernel, dim3((F + 63) / 64), dim3(64), 0, (hipStream_t)stream,
-                       out_uvxyz, targets, F, H, root_mode, p1, p2, xyz);
+    switch (n_pts) {                     // one instantiation per joint count of JMIN..JMAX
+#define DPK_METRICS_CASE(N)                                                                                       \
+    case N:                                                                                                       \
+        dpk_metrics::launch<N>(out_uvxyz, targets, F, H, root_mode, p1, p2, xyz, (hipStream_t)stream);            \
+        break;
+        DPK_METRICS_CASE(2) DPK_METRICS_CASE(3) DPK_METRICS_CASE(4) DPK_METRICS_CASE(5) DPK_METRICS_CASE(6)
+        DPK_METRICS_CASE(7) DPK_METRICS_CASE(8) DPK_METRICS_CASE(9) DPK_METRICS_CASE(10) DPK_METRICS_CASE(11)
+        DPK_METRICS_CASE(12) DPK_METRICS_CASE(13) DPK_METRICS_CASE(14) DPK_METRICS_CASE(15) DPK_METRICS_CASE(16)
+        DPK_METRICS_CASE(17) DPK_METRICS_CASE(18) DPK_METRICS_CASE(19) DPK_METRICS_CASE(20) DPK_METRICS_CASE(21)
+        DPK_METRICS_CASE(22) DPK_METRICS_CASE(23) DPK_METRICS_CASE(24) DPK_METRICS_CASE(25) DPK_METRICS_CASE(26)
+        DPK_METRICS_CASE(27) DPK_METRICS_CASE(28) DPK_METRICS_CASE(29) DPK_METRICS_CASE(30) DPK_METRICS_CASE(31)
+        DPK_METRICS_CASE(32)
+#undef DPK_METRICS_CASE
+        default: return DPK_E_INVALID;
+    }
     return hipGetLastError() == hipSuccess ? DPK_OK : DPK_E_HIP;
+}
+
+extern "C" int dpk_pose_metrics(const float* out_uvxyz, const float* targets, int F, int H, int root_mode,
+                                double* p1, double* p2, float* xyz, void* stream) {
+    return dpk_pose_metrics_n(out_uvxyz, targets, F, H, 17, root_mode, p1, p2, xyz, stream);
 }

@@ -18,7 +18,7 @@ DEFAULT_SEED = 19960903
 
 
 def synthetic_batch(n_frames: int, seed: int = DEFAULT_SEED, num_pts: int = 17):
-    """Return (uvxyz (B,17,5) f32, targets_3d (B,17,3) f32) for B = n_frames."""
+    """Return (uvxyz (B,num_pts,5) f32, targets_3d (B,num_pts,3) f32) for B = n_frames."""
     rng = np.random.Generator(np.random.PCG64(seed))
     uv = np.clip(rng.normal(0.0, 0.3, size=(n_frames, num_pts, 2)), -1.0, 1.0)
     xyz = rng.normal(0.0, 0.25, size=(n_frames, num_pts, 3))
@@ -41,14 +41,17 @@ def repeat_hypotheses(x: np.ndarray, test_times: int) -> np.ndarray:
     return np.ascontiguousarray(np.tile(x, (test_times, 1, 1)))
 
 
-def synthetic_eval_batches(n_frames: int, batch_size: int, seed: int = DEFAULT_SEED):
-    """Yield (input_2d [B,17,2], targets_3d [B,17,3], actions [B]) like test_hyber's loader
+def synthetic_eval_batches(n_frames: int, batch_size: int, seed: int = DEFAULT_SEED, num_pts: int = 17,
+                           actions=None):
+    """Yield (input_2d [B,num_pts,2], targets_3d [B,num_pts,3], actions [B]) like test_hyber's loader
     (runners/diffpose_frame.py:278-283, shuffle=False, so frames arrive grouped by action and
-    most batches hold a single action string; batches at a boundary mix two)."""
+    most batches hold a single action string; batches at a boundary mix two).  ``actions``: the
+    action names to spread the frames over (default ``metrics.TEST_ACTIONS``)."""
     from .metrics import TEST_ACTIONS
 
-    x, tgt = synthetic_batch(n_frames, seed=seed)
-    acts = np.array([f"{TEST_ACTIONS[(f * len(TEST_ACTIONS)) // max(n_frames, 1)]} 1" for f in range(n_frames)])
+    names = list(TEST_ACTIONS if actions is None else actions)
+    x, tgt = synthetic_batch(n_frames, seed=seed, num_pts=num_pts)
+    acts = np.array([f"{names[(f * len(names)) // max(n_frames, 1)]} 1" for f in range(n_frames)])
     for lo in range(0, n_frames, batch_size):
         hi = min(lo + batch_size, n_frames)
         yield np.ascontiguousarray(x[lo:hi, :, :2]), tgt[lo:hi], [str(a) for a in acts[lo:hi]]

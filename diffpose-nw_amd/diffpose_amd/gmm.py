@@ -5,7 +5,9 @@ Mirrors ``PoseGenerator_gmm`` (common/generators.py:9-56): the same constructor 
 6-tuple ``(uvxyz, noise_scale, pose_2d, pose_3d, action, camerapara)``.  The per-joint
 component choice — ``np.random.choice(kernel_n, 1, p=w)`` per joint in the reference — runs in
 ``dpk_gmm_sample`` for a whole batch at once: ``batch(indices)`` returns the collated batch as
-device tensors in one launch instead of 17 numpy calls per frame in DataLoader workers.
+device tensors in one launch instead of one numpy call per joint and frame in DataLoader workers.
+The joint count is the arrays' second dimension, 2..32 (joint 0 the root); 17 runs
+``dpk_gmm_sample``, any other ``dpk_gmm_sample_n``.
 
 Random stream: by default the uniforms come from numpy's global RandomState in the order the
 reference's ``__getitem__`` consumes them (frame by frame, joint by joint; ``choice`` draws one
@@ -22,8 +24,6 @@ import numpy as np
 import torch
 
 from . import _lib
-
-J = 17
 
 
 def numpy_atol(dtype) -> float:
@@ -44,8 +44,11 @@ class PoseGeneratorGMM:
         self._actions = reduce(lambda x, y: x + y, actions)
         self._camerapara = np.concatenate(camerapara)
         self._kernel_n = g.shape[2]
-        if g.ndim != 4 or g.shape[1] != J or g.shape[3] != 5:
-            raise ValueError(f"poses_2d_gmm must be (F,{J},kernel_n,5), got {g.shape}")
+        if g.ndim != 4 or g.shape[3] != 5:
+            raise ValueError(f"poses_2d_gmm must be (F,J,kernel_n,5), got {g.shape}")
+        J = self.n_pts = g.shape[1]
+        if not 2 <= J <= 32:
+            raise ValueError(f"the joint count must be 2..32, got poses_2d_gmm {g.shape}")
         if p3.shape != (g.shape[0], J, 3):
             raise ValueError(f"poses_3d must be ({g.shape[0]},{J},3), got {p3.shape}")
         assert p3.shape[0] == g.shape[0] and p3.shape[0] == len(self._actions)
@@ -68,12 +71,12 @@ class PoseGeneratorGMM:
         return int(index) % n                       # generators.py:26-29
 
     def batch(self, indices, u=None, seed=None, stream=None):
-        """Collated batch for frame ``indices``: (uvxyz [F,17,5], noise_scale [F,17,5], pose_2d
-        [F,17,2], pose_3d [F,17,3]) device tensors, plus the actions list and camerapara [F,...]
-        (host).  ``u`` [F,17] float64 uniforms, or None to draw them from np.random in the
+        """Collated batch for frame ``indices``: (uvxyz [F,J,5], noise_scale [F,J,5], pose_2d
+        [F,J,2], pose_3d [F,J,3]) device tensors, plus the actions list and camerapara [F,...]
+        (host).  ``u`` [F,J] float64 uniforms, or None to draw them from np.random in the
         reference's order, or ``seed`` for device-generated uniforms."""
         idx = np.asarray(indices, dtype=np.int64).reshape(-1)
-        F = idx.size
+        F, J = idx.size, self.n_pts
         uv = torch.empty(F, J, 5, dtype=torch.float32, device=self.device)
         ns = torch.empty(F, J, 5, dtype=torch.float32, device=self.device)
         if F:
@@ -89,12 +92,12 @@ class PoseGeneratorGMM:
             else:
                 u_ptr, s = None, int(seed) & 0xFFFFFFFFFFFFFFFF
             st = torch.cuda.current_stream(self.device) if stream is None else stream
-            fn = _lib.lib().dpk_gmm_sample_f64 if self._f64 else _lib.lib().dpk_gmm_sample
-            rc = fn(self._gmm.data_ptr(), self._p3.data_ptr(), self._gmm.shape[0],
-                                           self._kernel_n, idx_d.data_ptr(), F, u_ptr, s, self.atol,
+            name = "dpk_gmm_sample" + ("_f64" if self._f64 else "") + ("" if J == 17 else "_n")
+            head = (self._gmm.data_ptr(), self._p3.data_ptr(), self._gmm.shape[0]) + (() if J == 17 else (J,))
+            rc = getattr(_lib.lib(), name)(*head, self._kernel_n, idx_d.data_ptr(), F, u_ptr, s, self.atol,
                                            uv.data_ptr(), ns.data_ptr(), self._status.data_ptr(),
                                            ctypes.c_void_p(st.cuda_stream))
-            _lib.check(None, "dpk_gmm_sample", rc)
+            _lib.check(None, name, rc)
             flags = int(self._status.item())
             if flags & 1:
                 raise ValueError("probabilities are not non-negative")

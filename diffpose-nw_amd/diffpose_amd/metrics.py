@@ -30,39 +30,47 @@ TEST_ACTIONS = ["Directions", "Discussion", "Eating", "Greeting", "Phoning", "Ph
 def pose_errors(out_uvxyz: torch.Tensor, targets: torch.Tensor, test_times: int = 1, root_mode="quirk",
                 return_xyz: bool = False):
     """Per-frame (MPJPE, P-MPJPE) in metres, float64 device tensors of length F, for a sampler
-    output ``[test_times*F,17,5]`` (hypothesis-major) and ``targets_3d [F,17,3]``."""
+    output ``[test_times*F,J,5]`` (hypothesis-major) and ``targets_3d [F,J,3]``.  The joint count J
+    is ``out_uvxyz.shape[1]``, 2..32 (joint 0 the root); 17 runs ``dpk_pose_metrics``, any other
+    ``dpk_pose_metrics_n``."""
     for name, t in (("out_uvxyz", out_uvxyz), ("targets", targets)):
         if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32):
             raise TypeError(f"{name} must be a float32 CUDA(HIP) tensor")
     H = int(test_times)
-    if H < 1 or out_uvxyz.dim() != 3 or out_uvxyz.shape[1:] != (17, 5) or out_uvxyz.shape[0] % H:
-        raise ValueError(f"out_uvxyz must be (test_times*F, 17, 5), got {tuple(out_uvxyz.shape)}")
-    F = out_uvxyz.shape[0] // H
-    if targets.shape != (F, 17, 3):
-        raise ValueError(f"targets must be ({F}, 17, 3), got {tuple(targets.shape)}")
+    shapes = f"out_uvxyz {tuple(out_uvxyz.shape)}, targets {tuple(targets.shape)}"
+    if H < 1 or out_uvxyz.dim() != 3 or out_uvxyz.shape[2] != 5 or out_uvxyz.shape[0] % H:
+        raise ValueError(f"out_uvxyz must be (test_times*F, J, 5), got {shapes}")
+    F, J = out_uvxyz.shape[0] // H, out_uvxyz.shape[1]
+    if not 2 <= J <= 32:
+        raise ValueError(f"the joint count must be 2..32, got {shapes}")
+    if targets.shape != (F, J, 3):
+        raise ValueError(f"targets must be ({F}, {J}, 3), got {shapes}")
     if targets.device != out_uvxyz.device:
         raise ValueError("out_uvxyz and targets must be on the same device")
     out_uvxyz, targets = out_uvxyz.contiguous(), targets.contiguous()
     dev = out_uvxyz.device
     p1 = torch.empty(F, dtype=torch.float64, device=dev)
     p2 = torch.empty(F, dtype=torch.float64, device=dev)
-    xyz = torch.empty((F, 17, 3), dtype=torch.float32, device=dev) if return_xyz else None
+    xyz = torch.empty((F, J, 3), dtype=torch.float32, device=dev) if return_xyz else None
     stream = torch.cuda.current_stream(dev).cuda_stream
-    rc = _lib.lib().dpk_pose_metrics(out_uvxyz.data_ptr(), targets.data_ptr(), F, H, root_mode_id(root_mode),
-                                     p1.data_ptr(), p2.data_ptr(), xyz.data_ptr() if xyz is not None else None,
-                                     stream)
-    _lib.check(None, "dpk_pose_metrics", rc)
+    tail = (root_mode_id(root_mode), p1.data_ptr(), p2.data_ptr(), xyz.data_ptr() if xyz is not None else None,
+            stream)
+    if J == 17:
+        rc = _lib.lib().dpk_pose_metrics(out_uvxyz.data_ptr(), targets.data_ptr(), F, H, *tail)
+    else:
+        rc = _lib.lib().dpk_pose_metrics_n(out_uvxyz.data_ptr(), targets.data_ptr(), F, H, J, *tail)
+    _lib.check(None, "dpk_pose_metrics" if J == 17 else "dpk_pose_metrics_n", rc)
     return (p1, p2, xyz) if return_xyz else (p1, p2)
 
 
 def hypothesis_errors(out_uvxyz: torch.Tensor, targets: torch.Tensor, test_times: int = 1, root_mode="quirk"):
     """Per-hypothesis (MPJPE, P-MPJPE) in metres, float64 device tensors ``[test_times, F]``: every
-    hypothesis row of ``out_uvxyz [test_times*F,17,5]`` against its frame's target, not their mean
+    hypothesis row of ``out_uvxyz [test_times*F,J,5]`` against its frame's target, not their mean
     (``pose_errors``).  The same kernel on test_times*F "frames" of one hypothesis each.  Not in the
     reference, which books the hypothesis mean alone (runners/diffpose_frame.py:377-387)."""
     H = int(test_times)
     if H < 1 or not torch.is_tensor(targets) or targets.dim() != 3:
-        raise ValueError(f"test_times must be >= 1 and targets (F, 17, 3), got {test_times!r}")
+        raise ValueError(f"test_times must be >= 1 and targets (F, J, 3), got {test_times!r}")
     F = targets.shape[0]
     p1, p2 = pose_errors(out_uvxyz, targets.repeat(H, 1, 1), 1, root_mode)
     return p1.view(H, F), p2.view(H, F)

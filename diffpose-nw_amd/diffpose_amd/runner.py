@@ -36,6 +36,12 @@ The H36M ``.npz`` datasets are absent offline. ``test_hyber`` therefore takes an
 ``PoseGenerator_gmm`` loader delivers after its GMM draw. If none is given, it uses seeded
 synthetic batches (``data.synthetic_eval_batches``).
 
+Other skeletons: ``config.model.n_pts`` (2..32, joint 0 the root) with ``config.data.edges``, a list of
+``(i, j)`` joint pairs (required when ``n_pts`` is not 17; the default is the runner's 16 H36M edges),
+sets the graph of both models, the key mask, the noise draws and every batch shape (17 above reads
+``n_pts``).  ``config.data.actions``, if present, replaces the H36M action names of the per-action
+accounting.  Such models run the per-op path of the sampler.
+
 Checkpoints load with ``torch.load(weights_only=True)``.
 """
 from __future__ import annotations
@@ -53,7 +59,7 @@ import torch.distributed as dist
 from . import metrics
 from .data import shard_frames, synthetic_eval_batches
 from .dist import gather_frames, shard_rows
-from .gcndiff import HipGCNdiff, adj_mx_from_edges
+from .gcndiff import H36M_EDGES, HipGCNdiff, adj_mx_from_edges
 from .gcnpose import HipGCNpose
 from .schedule import get_beta_schedule, make_seq
 from .weights import load_checkpoint, synthetic_state_dict
@@ -87,7 +93,20 @@ class Diffpose:
         self.args = args
         self.config = config
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.src_mask = torch.ones(1, 1, 17, dtype=torch.bool, device=self.device)
+        self.n_pts = int(getattr(config.model, "n_pts", 17))
+        data = getattr(config, "data", None)
+        self.edges = getattr(data, "edges", None)
+        if self.edges is None:
+            if self.n_pts != 17:
+                raise ValueError(f"config.data.edges is required for n_pts = {self.n_pts}: the default graph is "
+                                 "the 17-joint H36M skeleton")
+            self.edges = H36M_EDGES
+        self.edges = tuple((int(i), int(j)) for i, j in self.edges)
+        if any(not (0 <= i < self.n_pts and 0 <= j < self.n_pts) for i, j in self.edges):
+            raise ValueError(f"config.data.edges names a joint outside 0..{self.n_pts - 1}: {self.edges}")
+        actions = getattr(data, "actions", None)
+        self.actions = list(metrics.TEST_ACTIONS if actions is None else actions)
+        self.src_mask = torch.ones(1, 1, self.n_pts, dtype=torch.bool, device=self.device)
         d = config.diffusion
         betas = get_beta_schedule(beta_schedule=d.beta_schedule, beta_start=d.beta_start, beta_end=d.beta_end,
                                   num_diffusion_timesteps=d.num_diffusion_timesteps)
@@ -102,14 +121,15 @@ class Diffpose:
         self.hypothesis_loss = None
 
     def _adj(self):
-        return adj_mx_from_edges()        # the runner's 16 H36M edges (diffpose_frame.py:120-125)
+        # by default the runner's 16 H36M edges (diffpose_frame.py:120-125)
+        return adj_mx_from_edges(self.n_pts, self.edges)
 
     def create_diffusion_model(self, model_path=None, state_dict=None):
         self.model_diff = HipGCNdiff(self._adj(), self.config, device=self.device)
         if model_path:
             self.model_diff.load_state_dict(load_checkpoint(model_path, kind="diff"))
         else:
-            self.model_diff.load_state_dict(state_dict if state_dict is not None else synthetic_state_dict())
+            self.model_diff.load_state_dict(state_dict if state_dict is not None else self._synthetic("diff"))
 
     def create_pose_model(self, model_path=None, state_dict=None):
         cfg = types.SimpleNamespace(**vars(self.config))
@@ -121,8 +141,11 @@ class Diffpose:
             self.model_pose.load_state_dict(load_checkpoint(model_path, kind="pose"))
         else:
             logging.info("initialize model randomly")
-            self.model_pose.load_state_dict(state_dict if state_dict is not None
-                                            else synthetic_state_dict(kind="pose"))
+            self.model_pose.load_state_dict(state_dict if state_dict is not None else self._synthetic("pose"))
+
+    def _synthetic(self, kind):
+        m = self.config.model
+        return synthetic_state_dict(kind=kind, hid=int(m.hid_dim), n_layers=int(m.num_layer), n_pts=self.n_pts)
 
     def _seq(self):
         te = self.config.testing
@@ -147,7 +170,7 @@ class Diffpose:
         src = getattr(self.args, "noise", "torch")
         if float(self.args.eta) == 0.0 or src in (None, "philox"):
             return None
-        full = torch.empty((H * n_frames, 17, 5), dtype=torch.float32, device=self.device)
+        full = torch.empty((H * n_frames, self.n_pts, 5), dtype=torch.float32, device=self.device)
         draw_noise(full, 1, src)                        # :359's e, consumed and dropped like the reference's
         z = draw_noise(full, K, src)
         if world == 1:
@@ -164,7 +187,7 @@ class Diffpose:
         src = getattr(self.args, "noise", "torch")
         if src in (None, "philox"):
             return None, None
-        full = torch.empty((H * n_frames, 17, 5), dtype=torch.float32, device=self.device)
+        full = torch.empty((H * n_frames, self.n_pts, 5), dtype=torch.float32, device=self.device)
         e = draw_noise(full, 1, src)[0]
         z = draw_noise(full, K, src) if float(self.args.eta) != 0.0 else None
         if world > 1:
@@ -176,7 +199,7 @@ class Diffpose:
     def _frame_errors(self, input_2d, targets_3d, H, seq, i, noise, root_mode, start=None):
         """Pose model, sampler and per-frame metrics for one (shard of a) batch: float64 device
         tensors (MPJPE, P-MPJPE) in metres, one per frame.  Also records the reference's per-batch
-        timing window under ``track_metrics``.  ``start``: (e rows or None, noise_scale rows [F,17,5] or
+        timing window under ``track_metrics``.  ``start``: (e rows or None, noise_scale rows [F,n_pts,5] or
         None) of the hypothesis start, which then runs inside the sampler launch."""
         F = input_2d.shape[0]
         if F == 0:
@@ -236,7 +259,10 @@ class Diffpose:
         seq = self._seq()
         self.diffusion_step_count = len(seq)        # runners/diffpose_frame.py:321
         if batches is None:
-            batches = synthetic_eval_batches(n_frames, self.config.training.batch_size, seed=self.args.seed)
+            other = {} if self.n_pts == 17 else {"num_pts": self.n_pts}
+            if self.actions != metrics.TEST_ACTIONS:
+                other["actions"] = self.actions
+            batches = synthetic_eval_batches(n_frames, self.config.training.batch_size, seed=self.args.seed, **other)
         root_mode = getattr(self.args, "root_mode", "quirk")
         world, rank, distributed = self._world()
         if frame_errors is None:
@@ -245,7 +271,7 @@ class Diffpose:
             self.model_pose.eval()
             self.model_diff.set_schedule(seq, self.betas, self.args.eta)
         epoch_p1, epoch_p2 = metrics.AverageMeter(), metrics.AverageMeter()
-        err = metrics.define_error_list(metrics.TEST_ACTIONS)
+        err = metrics.define_error_list(self.actions)
         self.inference_times, self.memory_usage = [], []
         self.pose_times, self.metrics_times = [], []
         i = -1
@@ -266,8 +292,9 @@ class Diffpose:
                     noise, e = self._batch_noise_start(B, H, len(seq), world, rank)
                     if noise_scale is not None:
                         noise_scale = np.asarray(noise_scale, dtype=np.float32)
-                        if noise_scale.shape != (B, 17, 5):
-                            raise ValueError(f"batch {i}: noise_scale must be ({B}, 17, 5), got {noise_scale.shape}")
+                        if noise_scale.shape != (B, self.n_pts, 5):
+                            raise ValueError(f"batch {i}: noise_scale must be ({B}, {self.n_pts}, 5), "
+                                             f"got {noise_scale.shape}")
                         noise_scale = np.ascontiguousarray(noise_scale[lo:hi])
                     kw["start"] = (e, noise_scale)
                 else:
@@ -281,7 +308,7 @@ class Diffpose:
                 p1h, p2h = p1.cpu().numpy(), p2.cpu().numpy()     # 16 B per frame to the host
                 epoch_p1.update(float(np.mean(p1h)) * 1000.0, B)
                 epoch_p2.update(float(np.mean(p2h)) * 1000.0, B)
-                metrics.test_calculation(p1h, p2h, actions, err)
+                metrics.test_calculation(p1h, p2h, actions, err, n_joints=self.n_pts)
         if self.track_metrics and self.inference_times:
             # Final computational metrics (runners/diffpose_frame.py:407-409)
             log_dir = getattr(self.args, "log_path", None)

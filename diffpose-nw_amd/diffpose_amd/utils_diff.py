@@ -99,7 +99,7 @@ def generalized_steps(x, src_mask, seq, model, b, **kwargs):
         # generic callable: host loop, HIP DDIM update
         upd = kwargs.get("updater")
         if upd is None:
-            upd = schedule_handle(x.device)
+            upd = schedule_handle(x.device, x.shape[1])
         upd.set_schedule(seq, b, eta)
         n = x.size(0)
         xs, x0s = [upd.q_sample(x, seed=seed, **start) if start else x], []
@@ -129,15 +129,16 @@ def _sched_cache() -> dict:
     return c
 
 
-def schedule_handle(device) -> HipGCNdiff:
-    """The cached schedule-only handle of ``device`` for the calling thread (created on first use)."""
+def schedule_handle(device, n_pts: int = 17) -> HipGCNdiff:
+    """The cached schedule-only handle of ``device`` for the calling thread (created on first use),
+    for poses of ``n_pts`` joints (``q_sample`` checks the pose shape and reads ``start_scale`` by it)."""
     dev = torch.device(device)
-    key = (dev.type, dev.index or 0)
+    key = (dev.type, dev.index or 0) + ((int(n_pts),) if int(n_pts) != 17 else ())
     cache = _sched_cache()
     upd = cache.get(key)
     if upd is None:
         upd = HipGCNdiff.__new__(HipGCNdiff)
-        _init_schedule_only(upd, dev)
+        _init_schedule_only(upd, dev, int(n_pts))
         cache[key] = upd
     return upd
 
@@ -152,20 +153,20 @@ def clear_schedule_handles() -> int:
     return n
 
 
-def _init_schedule_only(obj: HipGCNdiff, device) -> None:
+def _init_schedule_only(obj: HipGCNdiff, device, n_pts: int = 17) -> None:
     """A handle used only for its schedule table and the DDIM update kernel."""
     import ctypes
 
     from . import _lib
-    from .weights import COORDS, HID, N_HEAD, N_LAYERS, N_PTS
+    from .weights import COORDS, HID, N_HEAD, N_LAYERS
 
     obj.device = torch.device(device)
     L = _lib.lib()
-    cfg = _lib.DpkConfig(HID, N_LAYERS, N_HEAD, N_PTS, COORDS[0], COORDS[1], obj.device.index or 0)
+    cfg = _lib.DpkConfig(HID, N_LAYERS, N_HEAD, n_pts, COORDS[0], COORDS[1], obj.device.index or 0)
     h = ctypes.c_void_p()
     _lib.check(None, "dpk_create", L.dpk_create(ctypes.byref(cfg), ctypes.byref(h)))
     obj._h = h
-    obj.n_pts = N_PTS
+    obj.n_pts = n_pts
     obj._mask_key = None
     obj._mask_ref = None
     obj._sched_key = None

@@ -224,6 +224,15 @@ int dpk_pose(dpk_handle* h, const float* x2d_dev, float* xyz_dev, float* uvxyz_d
 int dpk_pose_metrics(const float* out_uvxyz_dev, const float* targets_dev, int F, int H, int root_mode,
                      double* p1_dev, double* p2_dev, float* xyz_dev, void* stream);
 
+/* dpk_pose_metrics for a skeleton of n_pts joints, 2 <= n_pts <= 32 (the range of dpk_create):
+ *   out_uvxyz_dev [H,F,n_pts,5], targets_dev [F,n_pts,3], xyz_dev [F,n_pts,3] or NULL
+ * Joint 0 is the root.  One kernel instance per joint count, each with the frame in registers (no
+ * private memory); the arithmetic and its order are those of the 17-joint call, which is this call
+ * with n_pts = 17.  An n_pts outside 2..32 returns DPK_E_INVALID before anything else is looked at;
+ * the other refusals are dpk_pose_metrics's. */
+int dpk_pose_metrics_n(const float* out_uvxyz_dev, const float* targets_dev, int F, int H, int n_pts,
+                       int root_mode, double* p1_dev, double* p2_dev, float* xyz_dev, void* stream);
+
 /* GMM 2D-keypoint sampling of the input pipeline: replaces
  * PoseGenerator_gmm.__getitem__ (common/generators.py:24-53) for a whole batch.
  *   gmm_dev      [n_src,17,kernel_n,5] fp32  per joint: [w, mu_u, mu_v, var_u, var_v] x kernel_n
@@ -251,6 +260,19 @@ int dpk_gmm_sample(const float* gmm_dev, const float* poses3d_dev, int n_src, in
 int dpk_gmm_sample_f64(const double* gmm_dev, const double* poses3d_dev, int n_src, int kernel_n,
                        const int64_t* index_dev, int F, const double* u_dev, uint64_t seed, double atol,
                        float* uvxyz_dev, float* noise_scale_dev, int* status_dev, void* stream);
+
+/* dpk_gmm_sample / dpk_gmm_sample_f64 for a skeleton of n_pts joints, 2 <= n_pts <= 32:
+ *   gmm_dev [n_src,n_pts,kernel_n,5], poses3d_dev [n_src,n_pts,3], u_dev [F,n_pts] or NULL,
+ *   uvxyz_dev, noise_scale_dev [F,n_pts,5]
+ * Joint 0 is the root.  The seeded uniform of (frame f, joint j) is keyed by f * n_pts + j.  The
+ * 17-joint calls are these with n_pts = 17.  An n_pts outside 2..32 returns DPK_E_INVALID before
+ * anything else is looked at; the other refusals are dpk_gmm_sample's. */
+int dpk_gmm_sample_n(const float* gmm_dev, const float* poses3d_dev, int n_src, int n_pts, int kernel_n,
+                     const int64_t* index_dev, int F, const double* u_dev, uint64_t seed, double atol,
+                     float* uvxyz_dev, float* noise_scale_dev, int* status_dev, void* stream);
+int dpk_gmm_sample_f64_n(const double* gmm_dev, const double* poses3d_dev, int n_src, int n_pts, int kernel_n,
+                         const int64_t* index_dev, int F, const double* u_dev, uint64_t seed, double atol,
+                         float* uvxyz_dev, float* noise_scale_dev, int* status_dev, void* stream);
 
 /* GEMM arithmetic of the sampler's transformer/ResChebGC GEMMs (not part of the reference
  * interface; the reference computes everything in fp32 on its device):
