@@ -8,7 +8,7 @@
 #include "dpk_pack.inc"
 
 // the GCNpose kernels (coords 2 -> 3) are compiled for the shipped shape's 4-wave tiles alone
-constexpr InstShape SHAPE = {D, NH, J, NL, P, NW, NT, SM_FLOATS * 4, (size_t)NL * D, GEMM_MODES, MODE_BF16 && NW == 4,
+constexpr InstShape SHAPE = {D, NH, J, NL, J_MIN, P, NW, NT, SM_FLOATS * 4, (size_t)NL * D, GEMM_MODES, MODE_BF16 && NW == 4,
                              CIN, COUT, ARENA_FLOATS, TEMB_FLOATS, MODE_F16X3 ? ARENA16_BYTES : 0,
                              MODE_BF16 ? ARENA16_BYTES / 2 : 0, pack_model};
 
@@ -21,27 +21,45 @@ static void fused_temb(const float* temb, const float* t, int stride, int count,
 // the noise source (the caller's draws, ZM = 1, or counter-based) and the GEMM mode gm (0 fp32 from W;
 // 1 f16x3 / 2 bf16 from W16: each compiled where the instance's descriptor has the mode, SHAPE.modes; a mode it
 // lacks never gets here, check_ready refuses it).  ST: the hypothesis start (dpk_sample_start, M_SAMPLE only).
-template <int MODE, bool SP, int ZM, bool ST = false>
+// PD: the padded-tile kernels (a.n_pts < 17; dense graph, fp32 and f16x3: bf16 is refused for such a handle).
+template <int MODE, bool SP, int ZM, bool ST = false, bool PD = false>
 static void launch_gemm_mode(int gm, dim3 grid, size_t shmem, hipStream_t st, const SampleArgs& a, const float* W,
                              const char* W16) {
     if constexpr (SHAPE.has_mode(1)) {
         if (gm == 1) {
-            hipLaunchKernelGGL((sample_kernel<MODE, SP, 1, ZM, ST>), grid, dim3(NT), shmem, st, a, W, W16);
+            hipLaunchKernelGGL((sample_kernel<MODE, SP, 1, ZM, ST, PD>), grid, dim3(NT), shmem, st, a, W, W16);
             return;
         }
     }
-    if constexpr (SHAPE.has_mode(2)) {
+    if constexpr (SHAPE.has_mode(2) && !PD) {
         if (gm == 2) {
-            hipLaunchKernelGGL((sample_kernel<MODE, SP, 2, ZM, ST>), grid, dim3(NT), shmem, st, a, W, W16);
+            hipLaunchKernelGGL((sample_kernel<MODE, SP, 2, ZM, ST, PD>), grid, dim3(NT), shmem, st, a, W, W16);
             return;
         }
     }
-    hipLaunchKernelGGL((sample_kernel<MODE, SP, 0, ZM, ST>), grid, dim3(NT), shmem, st, a, W, W16);
+    hipLaunchKernelGGL((sample_kernel<MODE, SP, 0, ZM, ST, PD>), grid, dim3(NT), shmem, st, a, W, W16);
 }
 template <int MODE>
 static void launch_sample(bool sparse, int gm, int blocks, size_t shmem, hipStream_t st, const SampleArgs& a,
                           const float* W, const char* W16) {
     const dim3 grid((unsigned)blocks);
+    if constexpr (PADDED && MODE != M_POSE) {
+        if (a.n_pts != J) {     // a padded handle: its arena is never sparse (pack_model)
+            if constexpr (MODE == M_SAMPLE) {
+                if (a.start_on) {
+                    if (a.noise) launch_gemm_mode<MODE, false, 1, true, true>(gm, grid, shmem, st, a, W, W16);
+                    else launch_gemm_mode<MODE, false, 0, true, true>(gm, grid, shmem, st, a, W, W16);
+                    return;
+                }
+                if (a.noise) {
+                    launch_gemm_mode<MODE, false, 1, false, true>(gm, grid, shmem, st, a, W, W16);
+                    return;
+                }
+            }
+            launch_gemm_mode<MODE, false, 0, false, true>(gm, grid, shmem, st, a, W, W16);
+            return;
+        }
+    }
     if constexpr (MODE == M_SAMPLE) {
         if (a.start_on) {
             if (a.noise) {

@@ -110,6 +110,9 @@ struct SampleArgs {
     float start_sb;       // sqrtf(1 - alpha_bar[t_start + 1])
     const float* start_scale;   // [start_scale_rows][17][5], pose n reads row n % start_scale_rows; null: ones
     int start_scale_rows;
+    // joints of the handle's model: 17, or 2..16 on padded tiles (the PAD kernels; every [..][17][5] above is then
+    // [..][n_pts][5]).  In the padding ahead of the next pointer: no other field's offset moves
+    int n_pts;
     const float* start_noise;   // [N][17][5] the caller's draws e, or null: normal_noise(seed, -1, element)
 #if DPK_TRACE
     unsigned long long* trace;   // [blocks][NW][TRACE_SLOTS]
@@ -143,7 +146,10 @@ namespace dpk {
 // The same 4-pose tile on 8 waves, two per SIMD (dpk_layout.inc DPK_NW): each SIMD's GEMM column tiles split
 // between its two waves, the per-pose phases split between the two waves of a pose as in the 2-pose tile.
 // At most 256 registers per lane; dpk_set_tile_waves chooses between this instance and dpk per GEMM mode.
+// (the sibling tiles of the shipped shape carry no padded kernels: DPK_PADDED 0, dpk_layout.inc)
 #define DPK_NW 8
+#undef DPK_PADDED
+#define DPK_PADDED 0
 namespace dpk8 {
 #include "dpk_sampler.inc"
 #include "dpk_genfused.inc"
@@ -155,6 +161,7 @@ namespace dpk2 {
 #include "dpk_sampler.inc"
 #include "dpk_genfused.inc"
 }  // namespace dpk2
+#undef DPK_PADDED
 // The persistent sampler at a wider model (round 5): hid 128 / 8 heads (d_k 16), 2-pose tiles (4-pose
 // tiles of 128-wide rows do not fit 160 KB of LDS), fp32 or f16x3 GEMMs; a handle of that shape runs it instead of the
 // per-op launches of dpk_generic.inc
@@ -324,8 +331,12 @@ static int fail(dpk_handle* h, int code, const std::string& msg) {
     return code;
 }
 
-// The gemm modes the handle's path runs, bit m for mode m: its sampler instance's, or fp32 alone per op
-static int gemm_modes(const dpk_handle* h) { return h->w.inst ? h->w.inst->modes : 1; }
+// Does the handle's model ride padded in its instance's tiles (fewer joints than the tile's 17)?
+static bool padded(const dpk_handle* h) { return h->w.inst && h->n_pts != h->w.inst->J; }
+
+// The gemm modes the handle's path runs, bit m for mode m: its sampler instance's (a padded handle: without bf16,
+// whose kernels are built for 17 joints alone), or fp32 alone per op
+static int gemm_modes(const dpk_handle* h) { return h->w.inst ? (padded(h) ? h->w.inst->modes & 3 : h->w.inst->modes) : 1; }
 
 // `launch` (returns a DPK code) on `st`, between an event pair when the handle is profiling (dpk_profile;
 // never under a capture)
@@ -615,11 +626,12 @@ static void launch_tiles(dpk_handle* h, const SamplerInst* tile, int mode, int b
 // of a 4-pose tile's time), one per CU, in a second launch after the full rounds.  Each
 // workgroup's result depends only on its own poses.
 // Both plans need the 2-pose sibling (plan 2 falls back on plan 1): an instance without one (the other
-// widths) runs ceil(N / P) of its tiles in one launch.
+// widths) runs ceil(N / P) of its tiles in one launch, and so does a padded handle of any instance (the sibling
+// tiles have no padded kernels).
 static int launch_sampler(dpk_handle* h, int mode, hipStream_t st, SampleArgs a, bool cap) {
     const SamplerInst* in = h->w.inst;
     const int N = a.N, P = in->P;
-    if (!in->tail2) {
+    if (!in->tail2 || padded(h)) {
         launch_tiles(h, in, mode, (N + P - 1) / P, 0, st, a);
         HIPCHK(h, hipGetLastError());
         return DPK_OK;
@@ -702,6 +714,7 @@ static SampleArgs eps_args(const dpk_handle* h, const float* arena, const float*
     a.mask = h->mask;
     a.pmask = h->pmask;
     a.num_layers = h->num_layers;
+    a.n_pts = h->n_pts;
     return a;
 }
 static SampleArgs sample_args(const dpk_handle* h, const float* arena, const float* tproj, const Sched* sc,
@@ -766,6 +779,13 @@ DPK_INST(dpkn4, {launch_sample<M_SAMPLE>, launch_sample<M_EPS>, nullptr}, nullpt
 #undef DPK_INST
 
 // dpk_create gives a handle the first entry that fits its config; a config none fits runs per op (GenModel)
+// A GCNdiff model of fewer than 17 joints fits its width's entry as padded tiles (InstShape::fits) and gets it
+// from DPK_PAD_MIN joints up: the smallest measured count from which upward the padded tile beat the per-op path by
+// more than 1 % at hid 96 / 4 x 5 layers, hid 128 / 8 x 5 and hid 64 / 2 x 2 alike (B=1024, K=50, fp32, medians of 9
+// alternating pairs; profiles/padded_joints_bench.txt).  A padded tile costs what 17 joints cost, the per-op path
+// grows with the rows: hid 96 and hid 64 won from the smallest count measured (4: 0.77, 0.57 of the per-op time),
+// the 2-pose tiles of hid 128 from 7 (0.93; 1.03 at 6, 1.26 at 4), so one constant for every width is 7
+constexpr int DPK_PAD_MIN = 7;
 constexpr const SamplerInst* INSTANCES[] = {&dpk::INST, &dpkw::INST, &dpkw4::INST, &dpkn::INST, &dpkn4::INST};
 constexpr bool instances_consistent() {
     for (const SamplerInst* i : INSTANCES) {
@@ -854,8 +874,13 @@ int dpk_create(const dpk_config* cfg, dpk_handle** out) {
     const char* fg = getenv("DPK_FORCE_GENERIC");
     const char* fe = getenv("DPK_GEN_FUSED");
     const bool no_inst = fg && atoi(fg) != 0, no_widths = fe && atoi(fe) == 0;
+    // fewer joints than the tiles' 17 ride padded from DPK_PAD_MIN joints up (DPK_PAD_MIN_JOINTS=2: every count,
+    // 17: none); below it the per-op path
+    int pad_min = DPK_PAD_MIN;
+    if (const char* pm = getenv("DPK_PAD_MIN_JOINTS")) pad_min = atoi(pm);
+    const bool no_pad = cfg->n_pts != J && cfg->n_pts < pad_min;
     for (const SamplerInst* i : INSTANCES)
-        if (!h->w.inst && !no_inst && !(no_widths && i != &dpk::INST) &&
+        if (!h->w.inst && !no_inst && !no_pad && !(no_widths && i != &dpk::INST) &&
             i->fits(cfg->hid_dim, cfg->n_head, cfg->n_pts, cfg->num_layers, cfg->coords_in, cfg->coords_out, kind))
             h->w.inst = i;
     if (!h->w.inst) {
@@ -1142,7 +1167,7 @@ int dpk_sample_start(dpk_handle* h, const float* x, float* out, float* xs, float
         h->w.inst->temb(h->w.temb, sc->coef + 5, 6, sc->K, tps, st);
     }
     // xs[0]: x, or with the start on x_T, which the kernel writes
-    if (xs && !start_on) HIPCHK(h, hipMemcpyAsync(xs, x, (size_t)N * PE * 4, hipMemcpyDeviceToDevice, st));
+    if (xs && !start_on) HIPCHK(h, hipMemcpyAsync(xs, x, (size_t)N * h->n_pts * CIN * 4, hipMemcpyDeviceToDevice, st));
     SampleArgs a = sample_args(h, h->w.arena, tps, sc, x, out, xs, x0s, N, seed, noise);
     if (start_on) {
         a.start_on = 1;
@@ -1182,7 +1207,7 @@ int dpk_q_sample(dpk_handle* h, const float* x, float* xT, int N, int t_start, c
     bool cap = false;
     if ((rc = capturing(h, st, &cap))) return rc;
     if (!cap) cap_sweep(h);
-    gen_qsample(st, x, xT, nullptr, N, h->gen ? h->gen->s.J * h->gen->s.cin : PE, start, seed);
+    gen_qsample(st, x, xT, nullptr, N, h->gen ? h->gen->s.J * h->gen->s.cin : h->n_pts * CIN, start, seed);
     HIPCHK(h, hipGetLastError());
     return DPK_OK;
 }
@@ -1208,9 +1233,15 @@ int dpk_set_gemm_mode(dpk_handle* h, int mode) {
     if (!h) return DPK_E_INVALID;
     if (mode < 0 || mode > 2)
         return fail(h, DPK_E_INVALID, "dpk_set_gemm_mode: mode must be 0 (fp32), 1 (3xfp16) or 2 (bf16)");
+    // a padded handle names its joint count at the set (the other refusals of a mode come at the call, check_ready)
+    if (mode == 2 && padded(h))
+        return fail(h, DPK_E_UNSUPPORTED, "dpk_set_gemm_mode: gemm mode 2 (bf16) is built for 17 joints; this handle has " +
+                                              std::to_string(h->n_pts) + " joints on padded tiles (fp32 and f16x3)");
     h->gemm_mode = mode;
     return DPK_OK;
 }
+
+int dpk_fused(const dpk_handle* h) { return h && h->w.inst ? 1 : 0; }
 
 int dpk_gemm_modes(const dpk_handle* h) { return h ? gemm_modes(h) : 0; }
 
@@ -1218,6 +1249,9 @@ int dpk_set_tile_waves(dpk_handle* h, int waves) {
     if (!h) return DPK_E_INVALID;
     if (waves != 0 && waves != 4 && waves != 8)
         return fail(h, DPK_E_INVALID, "dpk_set_tile_waves: waves must be 0 (the GEMM mode's default), 4 or 8");
+    if (waves == 8 && padded(h))
+        return fail(h, DPK_E_UNSUPPORTED, "dpk_set_tile_waves: the 8-wave tile is compiled for 17 joints; this handle has " +
+                                              std::to_string(h->n_pts) + " joints on padded 4-wave tiles");
     if (waves == 8 && !(h->w.inst && h->w.inst->wave8))
         return fail(h, DPK_E_UNSUPPORTED, "dpk_set_tile_waves: the 8-wave tile is compiled for hid 96 / 4 heads / 17 joints");
     h->tile_waves = waves;

@@ -37,6 +37,16 @@ constexpr bool MODE_F16X3 = DPK_F16X3 != 0;
 constexpr bool MODE_BF16 = D == 96 && NH == 4;
 constexpr int GEMM_MODES = 1 | (MODE_F16X3 ? 2 : 0) | (MODE_BF16 ? 4 : 0);   // bit m: gemm mode m
 
+// Padded tiles: a GCNdiff skeleton of 2..16 joints rides in the 17-row pose blocks of this instance, its graph
+// terms zero-embedded by pack_model and the rows past its joint count dead (dpk_sampler.inc: the PAD kernels,
+// dense graph, fp32 and f16x3).  Compiled for every table entry's primary tile; the sibling tiles (8 waves, the
+// 2-pose tail tile) set DPK_PADDED 0: launch_sampler runs a padded handle on plain primary tiles.
+#ifndef DPK_PADDED
+#define DPK_PADDED 1
+#endif
+constexpr bool PADDED = DPK_PADDED != 0;
+constexpr int J_MIN = PADDED ? 2 : J;        // fewest joints a GCNdiff handle of this instance may have
+
 // workgroup tile.  DPK_P (poses per workgroup) is set by the including file: 4 for the main sampler (one
 // workgroup per CU), 2 for the half-size tail tiles that balance the last round of a batch (launch_sampler)
 // and for the width-128 instances.  Both run one workgroup per CU, 4 waves (one per SIMD).  DPK_NW 8 (4-pose

@@ -57,6 +57,9 @@ static float pack16(uint16_t* dst, int Kreal, int Nreal, int KB32, int NC, F w) 
 
 // Everything the instance's kernels read, repacked from the staging `s` (a model of this instance's width,
 // 17 joints, at most NL layers; GCNdiff, or GCNpose with coords 2 -> 3): layers past s.L stay zero.
+// A staging of n = s.J < 17 joints (GCNdiff on padded tiles): its graph matrices (T1, T2, every layer's L_g,
+// all normalised at size n by the staging) are read at stride n and zero-embedded into the 17 x 17 blocks, so a
+// padded row neither gives to nor takes from a real one; such a model runs the dense-graph kernels.
 // half: also the split-fp16 and bf16 copies of the layer GEMMs' weights, each where the instance has its gemm
 // mode (MODE_F16X3, MODE_BF16), and w16_ok.
 static void pack_model(const Stage& s, Packed& out, bool half) {
@@ -69,6 +72,13 @@ static void pack_model(const Stage& s, Packed& out, bool half) {
     out.abf.assign(bf ? ARENA16_BYTES / 4 : 0, 0);     // bf16 blocks: half the bytes
     float* A = out.arena.data();
     float w16max = 0.f;             // largest |64 w| of the split-fp16 GEMM weights
+    const int n = s.J;              // the model's joints (<= J)
+    // a J x J matrix from the staging's n x n one: zeros outside
+    auto embed = [&](size_t at, float* dst) {
+        for (int i = 0; i < J; ++i)
+            for (int j = 0; j < J; ++j) dst[i * J + j] = (i < n && j < n) ? S[at + (size_t)i * n + j] : 0.f;
+    };
+    std::vector<float> LG(J * J), T1v(J * J), T2v(J * J);
     for (int l = 0; l < s.L; ++l) {
         const GenLayer& o = s.lay[l];
         float* Lw = A + (size_t)l * LAYER_FLOATS;
@@ -115,12 +125,13 @@ static void pack_model(const Stage& s, Packed& out, bool half) {
             Lw[OFF_LN1B + c] = S[o.n1b + c];
         }
         for (int c = 0; c < D2; ++c) Lw[OFF_BFC1 + c] = S[o.b1 + c];
-        for (int i = 0; i < J * J; ++i) Lw[OFF_LG + i] = S[o.lg + i];
+        embed(o.lg, LG.data());
+        for (int i = 0; i < J * J; ++i) Lw[OFF_LG + i] = LG[i];
         for (int q = 0; q < 5; ++q)
             for (int ln = 0; ln < 64; ++ln) {
                 const int i = 4 * q + (ln >> 4);
-                Lw[OFF_LGF + q * 64 + ln] = i < J ? S[o.lg + (ln & 15) * J + i] : 0.f;
-                Lw[OFF_LGF + (5 + q) * 64 + ln] = i < J ? S[o.lg + 16 * J + i] : 0.f;
+                Lw[OFF_LGF + q * 64 + ln] = i < J ? LG[(ln & 15) * J + i] : 0.f;
+                Lw[OFF_LGF + (5 + q) * 64 + ln] = i < J ? LG[16 * J + i] : 0.f;
             }
     }
     // fp16 hi parts must stay finite: |64 w| below the largest fp16 (65504), with margin
@@ -137,8 +148,10 @@ static void pack_model(const Stage& s, Packed& out, bool half) {
     for (int c = 0; c < D; ++c) A[OFF_BIN + c] = S[s.bin + c];
     for (int c = 0; c < 16; ++c) A[OFF_BOUT + c] = c < cout ? S[s.bout + c] : 0.f;
     // Chebyshev terms: dense, and the H36M-sparse forms, used when every nonzero lies inside the compiled pattern
-    const float* T1 = S + s.t1;
-    const float* T2 = S + s.t2;
+    embed(s.t1, T1v.data());
+    embed(s.t2, T2v.data());
+    const float* T1 = T1v.data();
+    const float* T2 = T2v.data();
     for (int i = 0; i < J * J; ++i) {
         A[OFF_CHEB + i] = T1[i];
         A[OFF_CHEB + J * J + i] = T2[i];
@@ -167,7 +180,7 @@ static void pack_model(const Stage& s, Packed& out, bool half) {
             memcpy(&row[2 * k + 1], &off, 4);
         }
     }
-    out.sparse = fits;
+    out.sparse = fits && n == J;    // fewer joints: the dense kernels (the padded ones are built for them alone)
     if (s.kind != 0) return;    // GCNpose has no timestep MLP
     // timestep MLP, transposed [in][out] (the staging rows are already [in][out])
     float* T = out.temb.data();

@@ -1407,10 +1407,14 @@ __device__ __forceinline__ s16x4 bf4(float a, float b, float c, float d) {
 // accumulate; the softmax and the normalisation stay fp32), joint 16's products included (A16): 4 + 4
 // MFMAs per head instead of 12 + 8 f32 MFMAs and the key-16 / query-16 VALU sums.  Lane group g's 8 score operands are dims {4g..4g+3} and {16+4g..16+4g+3} (zero
 // past d_k), the same k-permutation on both operands.
-template <int GA = 0, class Hook = NoHook>
+// PADK (padded tiles: a pose of nk < 17 joints, rows nk..16 dead): keys nk..16 are excluded hard, probability
+// exactly 0, on top of their mask bits being 0: the soft fill alone would leave a query whose keys are all
+// masked uniform over 17 keys where the nk-joint reference is uniform over nk.
+template <int GA = 0, bool PADK = false, class Hook = NoHook>
 __device__ __forceinline__ void attention_mma(const float* qkv, float* out, unsigned mask, int wave, int lane,
-                                              const Hook& hook = Hook{}) {
+                                              const Hook& hook = Hook{}, int nk = J) {
     static_assert(GA == 0 || DK == 24, "bf16 attention: d_k 24");
+    static_assert(GA == 0 || !PADK, "padded tiles: fp32 attention");
     // A16 (mode 2): the 17th joint's products on the matrix cores too: key 16's scores S[c][16] and
     // S[16][16] as a 16x16x32 bf16 product with key 16's row broadcast as the A operand (every output row
     // is the same dot products), and query 16's P.V with its probabilities broadcast as the B operand
@@ -1651,6 +1655,21 @@ __device__ __forceinline__ void attention_mma(const float* qkv, float* out, unsi
         p16[h] = ex(s_c16[h] - mx[h]);
         u16[h] = ex(s_1616[h] - my[h]);
     }
+    }
+    if constexpr (PADK) {
+        // dead keys out of numerators and denominators alike (their V rows are finite: 0 * v = 0); key 16 is
+        // dead on every padded tile
+#pragma unroll
+        for (int h = 0; h < HW; ++h) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const bool live = 4 * g + r < nk;
+                p[h][r] = live ? p[h][r] : 0.f;
+                u[h][r] = live ? u[h][r] : 0.f;
+            }
+            p16[h] = 0.f;
+            u16[h] = 0.f;
+        }
     }
     // ---- O^T = V^T P^T over keys 0..15 (4 MFMAs per column tile), then key 16 by FMA;
     //      query 16: this lane's keys 4g+r against V columns c and 16+c, summed over lane rows
@@ -2174,13 +2193,19 @@ __device__ __forceinline__ bool split_wait(const SampleArgs& a, int j, int tid) 
 // ---------------------------------------------------------------------------------------
 // The sampler: K DDIM steps (or one eps evaluation, or one GCNpose forward) for P poses
 // per workgroup.
-template <int MODE, bool SPARSE, int G16, int ZM = 0, bool START = false>
+template <int MODE, bool SPARSE, int G16, int ZM = 0, bool START = false, bool PAD = false>
 // ZM, the z of the DDIM update (sample mode): 0 counter-based draws when eta != 0, else 0; 1 the caller's
 // buffer (dpk_sample_noise).  Separate instantiations: the buffer read is not in the usual launch.
 // START (sample mode): the hypothesis start of dpk_sample_start in the tile's load of x_in.  A template flag and not
 // a launch-uniform branch on SampleArgs.start_on: the branch is a dozen instructions ahead of the step loop, yet with
 // it in the one kernel f16x3 measured 0.48 % slower than the parent build in 9 of 9 alternating pairs (fp32 equal,
 // bf16 K=100 0.41 % faster: code placement, profiles/hypothesis_start_ab.txt); START = false compiles the parent's kernel.
+// PAD (sample and eps modes, dense graph, fp32 and f16x3): a handle of a.n_pts = 2..16 joints on this tile.  LDS row
+// p*17 + j holds joint j of the tile's pose p when j < a.n_pts and is dead otherwise: global element
+// ((pose0 + p) * n_pts + j) * 5 + c for every load and store, the caller's draws and the counter-based ones alike;
+// the dead rows of the pose state are written as 0 at every step, and attention excludes the dead keys
+// (attention_mma PADK).  The packed graph terms are zero-embedded (dpk_pack.inc), so no live row reads a dead one.
+// A template flag for START's reason: PAD = false compiles the 17-joint kernels as they were.
 // `arena` is a separate restrict kernel argument: the compiler can then prove the weight arena
 // is never written during the launch and turns its wave-uniform loads (Laplacians, Chebyshev
 // terms, LayerNorm gains, biases) into scalar s_load (in the SampleArgs struct it cannot, and
@@ -2190,6 +2215,7 @@ __global__ void __launch_bounds__(NT, 1) sample_kernel(SampleArgs a, const float
                                                                const char* __restrict__ arena16) {
     constexpr bool EPS_MODE = MODE == M_EPS;
     constexpr bool POSE = MODE == M_POSE;
+    static_assert(!PAD || (PADDED && !SPARSE && !POSE && G16 != 2), "padded tiles: GCNdiff, dense graph, fp32 or f16x3");
     __shared__ __attribute__((aligned(16))) float sm[SM_FLOATS];
     float* XS = sm + SM_XS;
     float* B1 = sm + SM_B1;
@@ -2220,6 +2246,11 @@ __global__ void __launch_bounds__(NT, 1) sample_kernel(SampleArgs a, const float
     const int pose0 = a.pose_off + tile * P;
     const int npose = min(P, a.N - pose0);
     const int nvalid = npose * PE;
+    // PAD: joints and floats per pose in global memory; element i = (p*17 + j)*5 + c of the tile's pose state is
+    // live when p < npose and j < nj, and then global element gmap(i) of the [N][nj][5] arrays
+    const int nj = PAD ? a.n_pts : J, pe = PAD ? a.n_pts * CIN : PE;
+    auto live = [&](int i) { return i < nvalid && i % PE < pe; };
+    auto gmap = [&](int i) { return (size_t)(pose0 + i / PE) * pe + i % PE; };
     const float* W = arena;
     // the Chebyshev constants of input_prep / cheb_prep: the packed H36M-sparse values (uniform scalar
     // loads), or the dense T1 | T2 from their LDS copy (staged below for the output phase): as scalar
@@ -2229,6 +2260,7 @@ __global__ void __launch_bounds__(NT, 1) sample_kernel(SampleArgs a, const float
     // dpk_set_pose_masks, else the handle's one
     unsigned kmask = a.mask;
     if (a.pmask) kmask = a.pmask[min(pose0 + wave / (NW / P), a.N - 1)];
+    if constexpr (PAD) kmask &= (1u << nj) - 1u;
 
     if constexpr (POSE) {
         // uv into channels 0-1 of the 5-channel tile; the packed input weight is zero for 2-4
@@ -2253,7 +2285,20 @@ __global__ void __launch_bounds__(NT, 1) sample_kernel(SampleArgs a, const float
                 }
             }
         }
-        if (START && start) {
+        if (PAD && START && start) {
+            for (int i = tid; i < R * CIN; i += NT) {
+                float v = 0.f;
+                if (live(i)) {
+                    const size_t g = gmap(i);
+                    v = qsample_at(a.x_in[g], pose0 + i / PE, i % PE, pe, a.start_sa, a.start_sb, a.start_scale,
+                                   a.start_scale_rows, a.start_noise, a.seed);
+                    if (a.xs) a.xs[g] = v;
+                }
+                XST[i] = v;
+            }
+        } else if constexpr (PAD) {
+            for (int i = tid; i < R * CIN; i += NT) XST[i] = live(i) ? src[gmap(i)] : 0.f;
+        } else if (START && start) {
             // x_T of the tile's valid rows (padded rows stay 0); it is xs[0] of the trajectory
             for (int i = tid; i < R * CIN; i += NT) {
                 float v = 0.f;
@@ -2362,8 +2407,8 @@ __global__ void __launch_bounds__(NT, 1) sample_kernel(SampleArgs a, const float
                 };
                 if constexpr (!DPK_LATE(2) && !DPK_MID(2)) o_pre();
                 if (DPK_RUN(1)) {
-                    if constexpr (DPK_MID(2)) attention_mma<GG>(B2, B1, kmask, wave, lane, o_pre);
-                    else attention_mma<GG>(B2, B1, kmask, wave, lane);
+                    if constexpr (DPK_MID(2)) attention_mma<GG, PAD>(B2, B1, kmask, wave, lane, o_pre, nj);
+                    else attention_mma<GG, PAD>(B2, B1, kmask, wave, lane, NoHook{}, nj);
                 }
                 if constexpr (DPK_LATE(2)) {
                     __builtin_amdgcn_sched_barrier(0);
@@ -2550,8 +2595,8 @@ __global__ void __launch_bounds__(NT, 1) sample_kernel(SampleArgs a, const float
                 const float et = ((yp[j * LD2 + c] + a1) + a2) + bo[k];
                 const int r = p * J + j;
                 const int oidx = r * CIN + c;          // same as r*COUT+c (coords 5 -> 5)
-                const bool valid = oidx < nvalid;
-                const size_t gidx = (size_t)pose0 * PE + oidx;
+                const bool valid = PAD ? live(oidx) : oidx < nvalid;
+                const size_t gidx = PAD ? gmap(oidx) : (size_t)pose0 * PE + oidx;
                 if (POSE) {
                     B1[r * LDX + c] = et;
                 } else if (EPS_MODE) {
@@ -2560,14 +2605,14 @@ __global__ void __launch_bounds__(NT, 1) sample_kernel(SampleArgs a, const float
                     // c1 * z: the caller's per-step draws (the reference's randn_like, utils_diff.py:65)
                     // or counter-based noise
                     float z = 0.f;
-                    if constexpr (ZM == 1) z = valid ? a.noise[(size_t)s * a.N * PE + gidx] : 0.f;
+                    if constexpr (ZM == 1) z = valid ? a.noise[(size_t)s * a.N * pe + gidx] : 0.f;
                     else z = a.eta != 0.f ? normal_noise(a.seed, s, (long long)gidx) : 0.f;
                     float x0, xn;
                     ddim_elem(cf, XST[oidx], et, z, x0, xn);
-                    XST[oidx] = xn;
+                    XST[oidx] = (PAD && !valid) ? 0.f : xn;
                     if (valid) {
-                        if (a.x0s) a.x0s[(size_t)s * a.N * PE + gidx] = x0;
-                        if (a.xs) a.xs[(size_t)(s + 1) * a.N * PE + gidx] = xn;
+                        if (a.x0s) a.x0s[(size_t)s * a.N * pe + gidx] = x0;
+                        if (a.xs) a.xs[(size_t)(s + 1) * a.N * pe + gidx] = xn;
                     }
                 }
             }
@@ -2575,7 +2620,12 @@ __global__ void __launch_bounds__(NT, 1) sample_kernel(SampleArgs a, const float
         BAR();
     }
     if constexpr (MODE == M_SAMPLE) {
-        for (int i = tid; i < nvalid; i += NT) a.x_out[(size_t)pose0 * PE + i] = XST[i];
+        if constexpr (PAD) {
+            for (int i = tid; i < nvalid; i += NT)
+                if (live(i)) a.x_out[gmap(i)] = XST[i];
+        } else {
+            for (int i = tid; i < nvalid; i += NT) a.x_out[(size_t)pose0 * PE + i] = XST[i];
+        }
         if (half == 1) split_publish(a, tile - a.split_full, tid);
     } else if constexpr (POSE) {
         // inputs_xyz = model_pose(input_2d); inputs_xyz -= root; input_uvxyz = cat(uv, xyz).repeat(H)

@@ -38,7 +38,8 @@ struct Packed {
 // The shape and pack half of a sampler instance's descriptor (SHAPE in dpk_genfused.inc, one per instance
 // namespace; SamplerInst in dpk_kernels.hip adds the launch half)
 struct InstShape {
-    int D, NH, J, NL;            // hid_dim, n_head, n_pts, the most layers a launch runs
+    int D, NH, J, NL;            // hid_dim, n_head, n_pts of the tile, the most layers a launch runs
+    int Jmin;                    // fewest joints of a GCNdiff model it runs (below J: padded tiles, dpk_layout.inc)
     int P, NW, NT, lds_bytes;    // poses, waves and threads per workgroup; static LDS
     size_t tp;                   // floats of timestep projections per step (sample) or pose (eps): NL * D
     int modes;                   // bit m set: has gemm mode m's kernels and arena (0 fp32: always; 1 f16x3; 2 bf16)
@@ -48,10 +49,11 @@ struct InstShape {
     // half: also the half-width arenas of the modes the instance has (and w16_ok); false: neither
     void (*pack)(const Stage& s, Packed& out, bool half);
     constexpr bool has_mode(int m) const { return m >= 0 && m < 3 && (modes >> m & 1); }
-    // does this instance run a model of this shape?  kind 1 (GCNpose) is coords 2 -> 3 by definition
+    // does this instance run a model of this shape?  kind 1 (GCNpose) is coords 2 -> 3 by definition, and J joints
+    // alone; GCNdiff also on Jmin..J-1 joints, as padded tiles
     bool fits(int Dm, int Hm, int Jm, int Lm, int cin_, int cout_, int kind) const {
-        return Dm == D && Hm == NH && Jm == J && Lm >= 1 && Lm <= NL &&
-               (kind == 0 ? cin_ == cin && cout_ == cout : pose);
+        return Dm == D && Hm == NH && Lm >= 1 && Lm <= NL &&
+               (kind == 0 ? Jm >= Jmin && Jm <= J && cin_ == cin && cout_ == cout : Jm == J && pose);
     }
 };
 

@@ -19,7 +19,7 @@ ERRORS = {-1: "DPK_E_INVALID", -2: "DPK_E_UNSUPPORTED", -3: "DPK_E_HIP", -4: "DP
 EXPORTS = ("dpk_version", "dpk_create", "dpk_set_graph", "dpk_load_weights", "dpk_set_mask", "dpk_set_pose_masks",
            "dpk_set_schedule", "dpk_eps", "dpk_sample", "dpk_sample_noise", "dpk_sample_start", "dpk_q_sample", "dpk_ddim_update", "dpk_ddim_update_noise",
            "dpk_pose", "dpk_pose_metrics", "dpk_pose_metrics_n", "dpk_gmm_sample", "dpk_gmm_sample_f64", "dpk_gmm_sample_n",
-           "dpk_gmm_sample_f64_n", "dpk_set_gemm_mode", "dpk_gemm_modes",
+           "dpk_gmm_sample_f64_n", "dpk_set_gemm_mode", "dpk_gemm_modes", "dpk_fused",
            "dpk_set_tail_plan", "dpk_set_tile_waves", "dpk_debug_split", "dpk_debug_resources", "dpk_debug_generic_forms", "dpk_profile",
            "dpk_profile_read", "dpk_kernel_geometry", "dpk_last_error", "dpk_destroy")
 
@@ -89,6 +89,7 @@ def lib() -> ctypes.CDLL:
     L.dpk_gmm_sample_f64_n.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp, u64, ctypes.c_double, vp, vp, vp, vp]
     L.dpk_set_gemm_mode.argtypes = [vp, i32]
     L.dpk_gemm_modes.argtypes = [vp]
+    L.dpk_fused.argtypes = [vp]
     L.dpk_set_tail_plan.argtypes = [vp, i32]
     L.dpk_set_tile_waves.argtypes = [vp, i32]
     L.dpk_profile.argtypes = [vp, i32]

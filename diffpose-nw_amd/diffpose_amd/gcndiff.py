@@ -208,8 +208,15 @@ class _HipModel:
 
     def gemm_modes(self) -> int:
         """The GEMM modes this model's calls run (see dpk_gemm_modes): bit m set for mode m of GEMM_MODES,
-        so 0b111 at hid 96 / 4 heads, 0b011 at the other persistent-sampler shapes and 0b001 per op."""
+        so 0b111 at hid 96 / 4 heads on 17 joints, 0b011 at the other persistent-sampler shapes and on padded tiles
+        (fewer than 17 joints at any of them), and 0b001 per op."""
         return int(_lib.lib().dpk_gemm_modes(self._h))
+
+    @property
+    def fused(self) -> int:
+        """1 when a persistent sampler instance serves this model (17 joints, or fewer as padded tiles), 0 when
+        its calls run per op (see dpk_fused)."""
+        return int(_lib.lib().dpk_fused(self._h))
 
     TAIL_PLANS = {"four": 0, "two_pose": 1, "step_split": 2}
 

@@ -14,7 +14,7 @@
  *   - All tensor pointers are caller-owned DEVICE memory (fp32, row-major, contiguous)
  *     on the device the handle was created for; work is enqueued on `stream`
  *     (a hipStream_t, NULL = default stream) and is asynchronous.
- *   - Poses are (N, 17, 5) uvxyz: N poses x 17 joints x 5 channels.
+ *   - Poses are (N, n_pts, 5) uvxyz: N poses x the handle's joints (17 on Human3.6M) x 5 channels.
  *   - Return value 0 = OK, negative = error (DPK_E_*); dpk_last_error() has the text.
  *   - A handle is bound to one device and is not thread-safe: one handle per rank/thread.
  *   - Stream order: launches (dpk_sample / dpk_eps / dpk_pose / dpk_ddim_update) may be in
@@ -86,7 +86,11 @@ int dpk_version(void);
  * ZeroDivisionError for hid_dim 2 and 3; GCNpose has no embedding and takes hid_dim >= 2), 2 <= n_pts <= 32
  * and coords in == out (or [2,3]) runs the generic-shape path: the same model as per-op HIP kernels, or, for GCNdiff
  * at hid_dim 128 / n_head 8 or 4 and hid_dim 64 / n_head 2 or 4 on 17 joints (num_layer <= 5, coords [5,5]), the
- * persistent sampler compiled at that width (round 5).  The four width instances run gemm modes 0 (fp32) and
+ * persistent sampler compiled at that width (round 5).  GCNdiff on 2..16 joints at any of these five shapes runs
+ * the same persistent sampler as padded tiles (an n-joint pose in a 17-row pose block, its graph terms
+ * zero-embedded, the rows and attention keys past n dead), from DPK_PAD_MIN joints up (the environment variable
+ * DPK_PAD_MIN_JOINTS overrides it: 2 every count, 17 none), in gemm modes 0 and 1, on 4-wave tiles (dpk_fused says
+ * which path a handle got).  The four width instances run gemm modes 0 (fp32) and
  * 1 (f16x3), the per-op kernels mode 0 alone; a call in a mode the handle's path lacks fails with
  * DPK_E_UNSUPPORTED (dpk_gemm_modes says which it has).  Per-stream scratch grown on demand; under a caller's stream capture the
  * launches are recorded into the caller's graph from a capture-owned scratch (round 5; the first capture
@@ -138,15 +142,15 @@ int dpk_eps(dpk_handle* h, const float* x_dev, const float* t_dev, float* eps_de
 
 /* The whole K-step reverse loop of generalized_steps for N poses in ONE
  * persistent kernel (the per-step timestep projections come with the schedule).
- *   x_dev   [N,17,5] input x (= xs[0])
- *   out_dev [N,17,5] final sample xs[-1]
- *   xs_dev  [K+1,N,17,5] or NULL: full trajectory xs (xs[0] copied from x_dev; x_T under dpk_sample_start)
- *   x0s_dev [K,N,17,5]   or NULL: x0_preds
+ *   x_dev   [N,n_pts,5] input x (= xs[0])
+ *   out_dev [N,n_pts,5] final sample xs[-1]
+ *   xs_dev  [K+1,N,n_pts,5] or NULL: full trajectory xs (xs[0] copied from x_dev; x_T under dpk_sample_start)
+ *   x0s_dev [K,N,n_pts,5]   or NULL: x0_preds
  *   seed: noise stream for eta > 0 (counter-based, not torch.randn_like). */
 int dpk_sample(dpk_handle* h, const float* x_dev, float* out_dev, float* xs_dev, float* x0s_dev,
                int N, uint64_t seed, void* stream);
 
-/* dpk_sample with the caller's noise for eta > 0: noise_dev [K,N,17,5] fp32 device, slice k the
+/* dpk_sample with the caller's noise for eta > 0: noise_dev [K,N,n_pts,5] fp32 device, slice k the
  * draw z of the k-th executed step (t = seq[K-1-k]) in x' = sqrt(an)*x0 + c1*z + c2*et — what the
  * reference draws as torch.randn_like(x) once per step (common/utils_diff.py:65), so a caller that
  * draws the same K tensors reproduces the reference's eta > 0 trajectory.  NULL = counter-based
@@ -162,10 +166,10 @@ int dpk_sample_noise(dpk_handle* h, const float* x_dev, float* out_dev, float* x
  * roundings in that order (no FMA), so x_T is bitwise what torch computes for the same inputs.  The K steps
  * then run from x_T, and with xs_dev given xs[0] is x_T (written by the kernel; x_dev is not modified).
  *   t_start          < 0: no start; the call is dpk_sample_noise and the four arguments below are ignored
- *   scale_dev        [scale_rows,17,5] fp32 device or NULL (all ones).  Pose n reads row n % scale_rows, so
+ *   scale_dev        [scale_rows,n_pts,5] fp32 device or NULL (all ones).  Pose n reads row n % scale_rows, so
  *                    the [F,17,5] noise_scale of dpk_gmm_sample serves N = H*F hypothesis-major poses (the
  *                    reference's noise_scale.repeat(test_times,1,1)); scale_rows must divide N
- *   start_noise_dev  [N,17,5] fp32 device: the draws e (the reference's torch.randn_like(input_uvxyz), :359),
+ *   start_noise_dev  [N,n_pts,5] fp32 device: the draws e (the reference's torch.randn_like(input_uvxyz), :359),
  *                    or NULL: counter-based draws from `seed` at step -1, a counter domain disjoint from
  *                    eta's per-step draws (steps 0..K-1).  A pose's draw depends on the seed and its global
  *                    element index alone, not on tiles, tail plans or N
@@ -179,9 +183,9 @@ int dpk_sample_start(dpk_handle* h, const float* x_dev, float* out_dev, float* x
                      int t_start, const float* scale_dev, int scale_rows, const float* start_noise_dev,
                      void* stream);
 
-/* The start alone, x_T into xT_dev [N,17,5] (may be x_dev), for generic model callables whose loop runs on the
+/* The start alone, x_T into xT_dev [N,n_pts,5] (may be x_dev), for generic model callables whose loop runs on the
  * host: the sibling of dpk_ddim_update.  Arguments, arithmetic, draws and refusals as in dpk_sample_start
- * (t_start >= 0); needs a schedule (its alpha table), no weights.  On a per-op handle a pose has n_pts * coords_in floats. */
+ * (t_start >= 0); needs a schedule (its alpha table), no weights.  A pose has n_pts * coords_in floats on every handle. */
 int dpk_q_sample(dpk_handle* h, const float* x_dev, float* xT_dev, int N, int t_start,
                  const float* scale_dev, int scale_rows, const float* start_noise_dev,
                  uint64_t seed, void* stream);
@@ -288,8 +292,9 @@ int dpk_gmm_sample_f64_n(const double* gmm_dev, const double* poses3d_dev, int n
  * Applies to later dpk_sample / dpk_eps / dpk_pose calls on this handle.  Any of 0..2 is accepted
  * here; which of them a handle runs depends on its shape (dpk_gemm_modes): all three at hid 96 / 4
  * heads, modes 0 and 1 at hid 128 / 8 or 4 heads and hid 64 / 2 or 4 heads on the persistent sampler,
- * mode 0 alone per op.  A call in a mode the handle lacks returns DPK_E_UNSUPPORTED, its message naming
- * the mode and the shape.  Range: mode 1 needs every GEMM weight |w| < 1015 at every width (else those
+ * mode 0 alone per op; modes 0 and 1 at all five of those shapes on fewer than 17 joints (padded tiles), where mode 2
+ * is refused here, at the set, with the joint count in the message.  A call in a mode the handle lacks returns
+ * DPK_E_UNSUPPORTED, its message naming the mode and the shape.  Range: mode 1 needs every GEMM weight |w| < 1015 at every width (else those
  * calls return DPK_E_UNSUPPORTED) and GEMM inputs (LayerNorm/attention/graph/Chebyshev outputs) below
  * 65504 in magnitude; an overflow there shows as non-finite outputs. */
 int dpk_set_gemm_mode(dpk_handle* h, int mode);
@@ -297,6 +302,11 @@ int dpk_set_gemm_mode(dpk_handle* h, int mode);
 /* The gemm modes calls on this handle run: bit m set when mode m does (0b111 at hid 96 / 4 heads,
  * 0b011 on the four other persistent-sampler shapes, 0b001 on a per-op handle; 0 for a null handle). */
 int dpk_gemm_modes(const dpk_handle* h);
+
+/* 1 when a persistent sampler instance serves the handle (17 joints, or fewer on padded tiles), 0 when its calls
+ * run per op (NULL: 0).  A padded handle lists gemm modes 0b011 and refuses dpk_set_gemm_mode(h, 2) and
+ * dpk_set_tile_waves(h, 8) with DPK_E_UNSUPPORTED, naming its joint count. */
+int dpk_fused(const dpk_handle* h);
 
 /* How dpk_sample balances a partial last round of tiles (4 poses per workgroup, one workgroup
  * per CU per round; not part of the reference interface, which has no tiles):
@@ -322,7 +332,8 @@ int dpk_set_tail_plan(dpk_handle* h, int plan);
  * waves of a pose), or 0 (default): what the measurements chose for the handle's GEMM mode.  All
  * 4-pose tiles of a launch, the halves of step-split tiles included, run on the same instance, so
  * plans 0 and 2 stay bitwise equal; the 2-pose tail round, dpk_eps and dpk_pose always run 4 waves.
- * Both instances compute bitwise the same outputs.  Handles of another model shape accept 0 and 4.  With an
+ * Both instances compute bitwise the same outputs.  Handles of another model shape, or of fewer
+ * than 17 joints on padded tiles (plain 4-wave tiles, no tail plans), accept 0 and 4.  With an
  * adjacency outside the compiled H36M pattern (the dense Chebyshev path) 0 means 4 in every mode: the dense
  * 8-wave kernels exceed their register budget and run only when 8 is asked for.
  * The environment variable DPK_TILE_WAVES sets a new handle's value. */
