@@ -119,6 +119,19 @@ struct SampleArgs {
     int trace_step;
 #endif
 };
+
+// The launch census (dpk_debug_sampler_kernels; host bookkeeping only).  One word names one compiled sample_kernel:
+// the instance namespace's tile (DPK_TILE_ID: 0 dpk, 1 dpk8, 2 dpk2, 3 dpkw, 4 dpkw4, 5 dpkn, 6 dpkn4) in bits 0..3
+// and the kernel's six template arguments: MODE in bits 4..5, SPARSE in bit 6, G16 in bits 7..8, ZM in bit 9, START
+// in bit 10, PAD in bit 11.  Every hipLaunchKernelGGL site of launch_gemm_mode (dpk_genfused.inc) leaves the word of
+// the instantiation it names in last_kernel, built from that site's own template arguments; launch_tiles moves it
+// into the handle.
+constexpr uint32_t kernel_id(int tile, int mode, bool sparse, int g16, int zm, bool start, bool pad) {
+    return (uint32_t)tile | (uint32_t)mode << 4 | (uint32_t)sparse << 6 | (uint32_t)g16 << 7 | (uint32_t)zm << 9 |
+           (uint32_t)start << 10 | (uint32_t)pad << 11;
+}
+constexpr uint32_t KERNEL_NONE = ~0u;
+static thread_local uint32_t last_kernel = KERNEL_NONE;
 }  // namespace dpk_shared
 
 #include "dpk_stage.inc"
@@ -130,6 +143,8 @@ struct SamplerInst : InstShape {
     using Launch = void (*)(bool sparse, int gm, int blocks, size_t shmem, hipStream_t st,
                             const dpk_shared::SampleArgs& a, const float* W, const char* W16);
     void (*temb)(const float* temb, const float* t, int stride, int count, float* out, hipStream_t st);
+    // appends the id (dpk_shared::kernel_id) of every sample_kernel compiled for this tile (dpk_genfused.inc)
+    void (*kernels)(const SamplerInst& self, std::vector<uint32_t>& out);
     Launch launch[3];            // per kernel mode (M_SAMPLE, M_EPS, M_POSE); null: not compiled
     const SamplerInst* wave8;    // the same tile on 8 waves (M_SAMPLE only), or null
     const SamplerInst* tail2;    // the 2-pose tile of the same shape (launch_sampler's tail plans), or null
@@ -139,10 +154,12 @@ struct SamplerInst : InstShape {
 };
 
 #define DPK_P 4
+#define DPK_TILE_ID 0
 namespace dpk {
 #include "dpk_sampler.inc"
 #include "dpk_genfused.inc"
 }  // namespace dpk
+#undef DPK_TILE_ID
 // The same 4-pose tile on 8 waves, two per SIMD (dpk_layout.inc DPK_NW): each SIMD's GEMM column tiles split
 // between its two waves, the per-pose phases split between the two waves of a pose as in the 2-pose tile.
 // At most 256 registers per lane; dpk_set_tile_waves chooses between this instance and dpk per GEMM mode.
@@ -150,17 +167,21 @@ namespace dpk {
 #define DPK_NW 8
 #undef DPK_PADDED
 #define DPK_PADDED 0
+#define DPK_TILE_ID 1
 namespace dpk8 {
 #include "dpk_sampler.inc"
 #include "dpk_genfused.inc"
 }  // namespace dpk8
+#undef DPK_TILE_ID
 #undef DPK_NW
 #undef DPK_P
 #define DPK_P 2
+#define DPK_TILE_ID 2
 namespace dpk2 {
 #include "dpk_sampler.inc"
 #include "dpk_genfused.inc"
 }  // namespace dpk2
+#undef DPK_TILE_ID
 #undef DPK_PADDED
 // The persistent sampler at a wider model (round 5): hid 128 / 8 heads (d_k 16), 2-pose tiles (4-pose
 // tiles of 128-wide rows do not fit 160 KB of LDS), fp32 or f16x3 GEMMs; a handle of that shape runs it instead of the
@@ -171,10 +192,12 @@ namespace dpk2 {
 #undef DPK_NH
 #define DPK_D 128
 #define DPK_NH 8
+#define DPK_TILE_ID 3
 namespace dpkw {
 #include "dpk_sampler.inc"
 #include "dpk_genfused.inc"
 }  // namespace dpkw
+#undef DPK_TILE_ID
 #undef DPK_NH
 #undef DPK_D
 #undef DPK_P
@@ -182,10 +205,12 @@ namespace dpkw {
 #define DPK_P 2
 #define DPK_D 128
 #define DPK_NH 4
+#define DPK_TILE_ID 4
 namespace dpkw4 {
 #include "dpk_sampler.inc"
 #include "dpk_genfused.inc"
 }  // namespace dpkw4
+#undef DPK_TILE_ID
 #undef DPK_NH
 #undef DPK_D
 #undef DPK_P
@@ -194,16 +219,20 @@ namespace dpkw4 {
 #define DPK_P 4
 #define DPK_D 64
 #define DPK_NH 2
+#define DPK_TILE_ID 5
 namespace dpkn {
 #include "dpk_sampler.inc"
 #include "dpk_genfused.inc"
 }  // namespace dpkn
+#undef DPK_TILE_ID
 #undef DPK_NH
 #define DPK_NH 4
+#define DPK_TILE_ID 6
 namespace dpkn4 {
 #include "dpk_sampler.inc"
 #include "dpk_genfused.inc"
 }  // namespace dpkn4
+#undef DPK_TILE_ID
 #undef DPK_NH
 #undef DPK_D
 #undef DPK_P
@@ -319,6 +348,7 @@ struct dpk_handle {
     int pmask_n = 0;
     bool profiling = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_used, ev_free;
+    std::vector<uint32_t> kernels;   // the launch census: distinct sample_kernel ids since dpk_debug_sampler_kernels read them
 #if DPK_TRACE
     unsigned long long* trace = nullptr;
     size_t trace_len = 0;
@@ -609,7 +639,12 @@ static int tile_waves(const dpk_handle* h) {
 static void launch_tiles(dpk_handle* h, const SamplerInst* tile, int mode, int blocks, size_t shmem, hipStream_t st,
                          const SampleArgs& a) {
     const char* a16 = h->gemm_mode == 2 ? h->w.arenabf : h->w.arena16;
+    dpk_shared::last_kernel = dpk_shared::KERNEL_NONE;
     tile->launch[mode](h->w.pk.sparse, h->gemm_mode, blocks, shmem, st, a, h->w.arena, a16);
+    // the census: what the launch site said it launched (or recorded into a capture), not what was asked for above
+    const uint32_t id = dpk_shared::last_kernel;
+    if (id != dpk_shared::KERNEL_NONE && std::find(h->kernels.begin(), h->kernels.end(), id) == h->kernels.end())
+        h->kernels.push_back(id);
 }
 
 // The sampler over a.N poses.  One 4-pose workgroup per CU per round; a partial last round of r
@@ -764,9 +799,9 @@ DPK_LAUNCHER(dpk8, M_SAMPLE) DPK_LAUNCHER(dpk, M_SAMPLE) DPK_LAUNCHER(dpk2, M_SA
 DPK_LAUNCHER(dpk, M_POSE) DPK_LAUNCHER(dpk2, M_POSE)
 #undef DPK_LAUNCHER
 
-// The descriptors: {shape half, timestep MLP, {M_SAMPLE, M_EPS, M_POSE}, 8-wave sibling, 2-pose sibling, sched_tps}
+// The descriptors: {shape half, timestep MLP, kernel list, {M_SAMPLE, M_EPS, M_POSE}, 8-wave sibling, 2-pose sibling, sched_tps}
 #define DPK_INST(ns, ...) \
-    namespace ns { constexpr SamplerInst INST = {SHAPE, fused_temb, __VA_ARGS__}; }
+    namespace ns { constexpr SamplerInst INST = {SHAPE, fused_temb, list_kernels, __VA_ARGS__}; }
 // the shipped shape (hid 96 / 4 heads): its 8-wave and 2-pose tiles are reached through the 4-pose tile's entry
 DPK_INST(dpk8, {launch_sample<M_SAMPLE>, nullptr, nullptr}, nullptr, nullptr, true)
 DPK_INST(dpk2, {launch_sample<M_SAMPLE>, launch_sample<M_EPS>, launch_sample<M_POSE>}, nullptr, nullptr, true)
@@ -1347,6 +1382,21 @@ int dpk_debug_resources(dpk_handle* h, int* out, int n) {
 int dpk_debug_generic_forms(dpk_handle* h, unsigned* forms) {
     if (!h || !forms) return DPK_E_INVALID;
     *forms = gen_take_forms(h->gen);
+    return DPK_OK;
+}
+
+int dpk_debug_sampler_kernels(dpk_handle* h, uint32_t* ids, int cap, int* count) {
+    if (!count || cap < 0 || (cap > 0 && !ids)) return fail(h, DPK_E_INVALID, "dpk_debug_sampler_kernels: bad args");
+    std::vector<uint32_t> v;
+    if (h) {
+        v.swap(h->kernels);
+    } else {
+        for (const SamplerInst* i : INSTANCES)
+            for (const SamplerInst* t : {i, i->wave8, i->tail2})
+                if (t) t->kernels(*t, v);
+    }
+    for (int k = 0; k < cap && k < (int)v.size(); ++k) ids[k] = v[k];
+    *count = (int)v.size();
     return DPK_OK;
 }
 

@@ -20,7 +20,8 @@ EXPORTS = ("dpk_version", "dpk_create", "dpk_set_graph", "dpk_load_weights", "dp
            "dpk_set_schedule", "dpk_eps", "dpk_sample", "dpk_sample_noise", "dpk_sample_start", "dpk_q_sample", "dpk_ddim_update", "dpk_ddim_update_noise",
            "dpk_pose", "dpk_pose_metrics", "dpk_pose_metrics_n", "dpk_gmm_sample", "dpk_gmm_sample_f64", "dpk_gmm_sample_n",
            "dpk_gmm_sample_f64_n", "dpk_set_gemm_mode", "dpk_gemm_modes", "dpk_fused",
-           "dpk_set_tail_plan", "dpk_set_tile_waves", "dpk_debug_split", "dpk_debug_resources", "dpk_debug_generic_forms", "dpk_profile",
+           "dpk_set_tail_plan", "dpk_set_tile_waves", "dpk_debug_split", "dpk_debug_resources", "dpk_debug_generic_forms", "dpk_debug_sampler_kernels",
+           "dpk_profile",
            "dpk_profile_read", "dpk_kernel_geometry", "dpk_last_error", "dpk_destroy")
 
 
@@ -80,6 +81,7 @@ def lib() -> ctypes.CDLL:
     L.dpk_debug_split.argtypes = [vp, i32, ctypes.POINTER(i32)]
     L.dpk_debug_resources.argtypes = [vp, ctypes.POINTER(i32), i32]
     L.dpk_debug_generic_forms.argtypes = [vp, ctypes.POINTER(ctypes.c_uint)]
+    L.dpk_debug_sampler_kernels.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32), i32, ctypes.POINTER(i32)]
     L.dpk_pose.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
     L.dpk_pose_metrics.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp]
     L.dpk_gmm_sample.argtypes = [vp, vp, i32, i32, vp, i32, vp, u64, ctypes.c_double, vp, vp, vp, vp]
@@ -121,3 +123,40 @@ def kernel_geometry():
     a, b, c = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
     L.dpk_kernel_geometry(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c))
     return {"poses_per_workgroup": a.value, "threads_per_workgroup": b.value, "lds_bytes": c.value}
+
+
+# dpk_debug_sampler_kernels: the fields of a kernel id (include/diffpose_kernels.h)
+SAMPLER_TILES = ("dpk", "dpk8", "dpk2", "dpkw", "dpkw4", "dpkn", "dpkn4")
+SAMPLER_MODES = ("sample", "eps", "pose")
+SAMPLER_GEMMS = ("fp32", "f16x3", "bf16")
+
+
+def sampler_kernel_id(tile: str, mode: str, sparse: bool, gemm: str, zm: int = 0, start: bool = False,
+                      pad: bool = False) -> int:
+    """The id word of sample_kernel<mode, sparse, gemm, zm, start, pad> of ``tile``."""
+    return (SAMPLER_TILES.index(tile) | SAMPLER_MODES.index(mode) << 4 | int(bool(sparse)) << 6 |
+            SAMPLER_GEMMS.index(gemm) << 7 | int(zm) << 9 | int(bool(start)) << 10 | int(bool(pad)) << 11)
+
+
+def sampler_kernel_name(kid: int) -> str:
+    """A kernel id as text: tile/mode/graph/gemm/z<ZM>, then /start and /pad where set, e.g.
+    dpk8/sample/sparse/bf16/z1/start."""
+    name = "/".join((SAMPLER_TILES[kid & 15], SAMPLER_MODES[kid >> 4 & 3], "sparse" if kid >> 6 & 1 else "dense",
+                     SAMPLER_GEMMS[kid >> 7 & 3], f"z{kid >> 9 & 1}"))
+    return name + ("/start" if kid >> 10 & 1 else "") + ("/pad" if kid >> 11 & 1 else "")
+
+
+def sampler_kernels(handle) -> list:
+    """dpk_debug_sampler_kernels as names: what ``handle``'s calls launched since the last read, or with None
+    every sample_kernel compiled into the library."""
+    L = lib()
+    n = ctypes.c_int(0)
+    check(handle, "dpk_debug_sampler_kernels", L.dpk_debug_sampler_kernels(None, None, 0, ctypes.byref(n)))
+    buf = (ctypes.c_uint32 * max(n.value, 1))()       # a handle cannot have launched more than are compiled
+    check(handle, "dpk_debug_sampler_kernels", L.dpk_debug_sampler_kernels(handle, buf, len(buf), ctypes.byref(n)))
+    return [sampler_kernel_name(buf[i]) for i in range(min(n.value, len(buf)))]
+
+
+def compiled_sampler_kernels() -> list:
+    """The name of every sample_kernel instantiation compiled into the library, in the library's order."""
+    return sampler_kernels(None)

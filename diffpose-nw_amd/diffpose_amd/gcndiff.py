@@ -265,6 +265,12 @@ class _HipModel:
         _lib.check(self._h, "dpk_debug_generic_forms", _lib.lib().dpk_debug_generic_forms(self._h, ctypes.byref(w)))
         return {name for i, name in enumerate(self.GENERIC_FORMS) if (w.value >> i) & 1}
 
+    def debug_sampler_kernels(self) -> set:
+        """Test hook (dpk_debug_sampler_kernels): the names (_lib.sampler_kernel_name, e.g.
+        dpk8/sample/sparse/bf16/z1/start) of the persistent sampler's kernels this model's calls have launched, or
+        recorded into a capture, since the last read; empty on a per-op handle."""
+        return set(_lib.sampler_kernels(self._h))
+
     def profile(self, enable: bool = True) -> None:
         """Bracket each model-kernel launch with HIP events (see dpk_profile)."""
         _lib.check(self._h, "dpk_profile", _lib.lib().dpk_profile(self._h, 1 if enable else 0))

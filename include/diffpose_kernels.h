@@ -361,10 +361,21 @@ int dpk_profile_read(dpk_handle* h, float* ms_out, int cap, int* count);
  * 1 gemm_sk<4>, 2 gemm_sk<2>, 3..8 gemm<128|64|32> with 16-byte / scalar loads, 9..11 attention staged
  * + vector / staged + scalar / unstaged, 12..13 graph staged / unstaged, 14..15 cheb_basis staged /
  * unstaged).  Host bookkeeping only: it waits for nothing, and a K-step loop recorded as a hipGraph sets
- * its bits when it is recorded, not when it is replayed.  0 on a handle that runs a persistent sampler. */
+ * its bits when it is recorded, not when it is replayed.  0 on a handle that runs a persistent sampler.
+ * dpk_debug_sampler_kernels: which compiled kernels of the persistent sampler the handle's calls have launched
+ * since the last read, then cleared: up to `cap` distinct ids in ids[], their full number in *count (ids past
+ * `cap` are dropped: 256 words hold any answer).  An id names one sample_kernel<MODE, SPARSE, G16, ZM, START,
+ * PAD> of one tile: bits 0..3 the tile (0 dpk: hid 96 / 4 heads, 4 poses on 4 waves; 1 dpk8: on 8 waves; 2 dpk2:
+ * 2 poses; 3 dpkw: hid 128 / 8; 4 dpkw4: hid 128 / 4; 5 dpkn: hid 64 / 2; 6 dpkn4: hid 64 / 4), bits 4..5 MODE
+ * (0 sample, 1 eps, 2 pose), bit 6 SPARSE (the compiled H36M pattern), bits 7..8 G16 (the gemm mode), bit 9 ZM
+ * (the caller's noise), bit 10 START (dpk_sample_start), bit 11 PAD (fewer than 17 joints).  The id is written
+ * where the kernel is launched, from that launch's own template arguments.  Host bookkeeping only: it waits for
+ * nothing, and a captured launch counts when it is recorded, not when its graph is replayed.  A per-op handle
+ * returns 0 ids.  With h == NULL: every id compiled into the library (cap may be 0 to ask for *count alone). */
 int dpk_debug_split(dpk_handle* h, int mode, int* fallbacks);
 int dpk_debug_resources(dpk_handle* h, int* out, int n);
 int dpk_debug_generic_forms(dpk_handle* h, unsigned* forms);
+int dpk_debug_sampler_kernels(dpk_handle* h, uint32_t* ids, int cap, int* count);
 
 /* Poses per workgroup of the sampler kernel and its static LDS bytes (for docs/bench). */
 int dpk_kernel_geometry(int* poses_per_workgroup, int* threads_per_workgroup, int* lds_bytes);

@@ -271,6 +271,14 @@ EPS_CASES = (tuple(f"one/{i}" for i in range(5)) + ("mask_handle", "mask_pose", 
              + tuple(f"regime/{r}" for r in REGIMES))
 SAMPLE_CASES = ("sample/K1", "sample/K2")
 ALL_CASES = EPS_CASES + SAMPLE_CASES + ("pose",)
+# The cases tests/test_gpu_sampler_kernels.py adds so that every bf16 kernel of the persistent sampler has one
+# (tests/sampler_cells.py holds their bars): the K = 2 sampler on the dense adjacency, with the caller's noise at
+# eta 0.5, from the noised hypothesis start, in every combination the kernels are compiled in (flags after
+# sample/K2 in this order), and GCNpose on the dense adjacency.
+KERNEL_SAMPLE_FLAGS = tuple("".join(f) for f in
+                            (("/dense" * d, "/noise" * z, "/start" * st) for d in (0, 1) for z in (0, 1) for st in (0, 1)))
+KERNEL_CASES = tuple("sample/K2" + f for f in KERNEL_SAMPLE_FLAGS if f) + ("pose/dense",)
+SEED_KERNEL = 4444                        # the caller's noise, the start's draws and its scale
 
 
 @functools.lru_cache(maxsize=None)
@@ -299,10 +307,29 @@ def case(name):
         xkind = r if r in E.INPUTS else r[len("refinit_"):] if r.startswith("refinit_") else "baseline"
         c["x"] = _regime_x(xkind, c["x"])
     elif name.startswith("sample/"):
-        k = int(name[-1])
+        k = int(name.split("/")[1][1:])
         c["x"] = torch.from_numpy(synthetic_batch(N_SAMPLE, seed=SEED_SAMPLE)[0])
         c["t"] = None
         c["seq"], c["betas"] = {1: [30], 2: [12, 37]}[k], _betas(51)
+        flags = name.split("/")[2:]
+        assert name in SAMPLE_CASES or name in KERNEL_CASES, name
+        g = torch.Generator().manual_seed(SEED_KERNEL)
+        z, e = torch.randn((k,) + tuple(c["x"].shape), generator=g), torch.randn(c["x"].shape, generator=g)
+        sc = torch.ones(1, 17, 5)
+        sc[:, :, :2] = 0.25 + 2.0 * torch.rand((1, 17, 2), generator=g)
+        if "dense" in flags:
+            c["adj"] = adj_mx_from_edges(17, DENSE_EDGES)
+        if "noise" in flags:             # the z of the DDIM update: the caller's draws at eta 0.5
+            c["eta"], c["noise"] = E.ETA_NOISE, z
+        if "start" in flags:             # x_in is what the kernel is given; the loop runs from x, the torch x_T
+            c["start"] = dict(t_start=c["seq"][-1], start_scale=sc, start_noise=e)
+            c["x_in"], c["x"] = c["x"], E.start_xT(c["x"], e, sc, c["seq"][-1], c["betas"])
+    elif name == "pose/dense":
+        c["kind"] = "pose"
+        c["sd"] = one_layer_state_dict(synthetic_state_dict(kind="pose"), 0)
+        c["adj"] = adj_mx_from_edges(17, DENSE_EDGES)
+        c["x"] = c["x"][:, :, :2].contiguous()
+        c["t"] = None
     elif name == "pose":
         c["kind"] = "pose"
         c["sd"] = one_layer_state_dict(synthetic_state_dict(kind="pose"), 0)
@@ -325,7 +352,8 @@ def run(name, fwd=forward_bf16, **kw):
         if c["t"] is not None:
             return fwd(P, g, c["x"], c["mask"], c["t"], 1, HEADS, **kw)
         xs, x0s = O.generalized_steps(c["x"], c["mask"], c["seq"],
-                                      lambda a, m, t: fwd(P, g, a, m, t, 1, HEADS, **kw), c["betas"])
+                                      lambda a, m, t: fwd(P, g, a, m, t, 1, HEADS, **kw), c["betas"],
+                                      eta=c.get("eta", 0.0), noise=c.get("noise"))
         return torch.stack(x0s + [xs[-1]])
 
 

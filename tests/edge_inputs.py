@@ -1,6 +1,7 @@
 """Shared inputs of the numerical-edge tests (tests/test_oracle_fp64.py and tests/test_generic_forms_cpu.py
 on the CPU, tests/test_gpu_input_regimes.py, tests/test_gpu_pose_metrics.py and
-tests/test_gpu_generic_forms.py on the GPU): the input / weight / schedule / mask regimes outside the one
+tests/test_gpu_generic_forms.py on the GPU; tests/sampler_cells.py builds the persistent sampler's kernel table on
+regime / diff_oracles with the caller's noise and the hypothesis start): the input / weight / schedule / mask regimes outside the one
 every other parity test draws from, the model shapes that reach every kernel form of the per-op path, the
 float32 and float64 oracle runs on them, and the degenerate poses of the metrics kernel.  Everything comes
 from fixed seeds; nothing here touches a GPU.
@@ -14,13 +15,14 @@ whose outputs are not O(1) and never loosens the standing one.
 from __future__ import annotations
 
 import functools
+import math
 
 import numpy as np
 import torch
 
 from diffpose_amd.data import synthetic_batch
 from diffpose_amd.gcndiff import H36M_EDGES, adj_mx_from_edges
-from diffpose_amd.schedule import get_beta_schedule, make_seq
+from diffpose_amd.schedule import alpha_bar_table, get_beta_schedule, make_seq
 from diffpose_amd.weights import reference_init_state_dict, synthetic_state_dict
 from oracle import gcndiff_oracle as O
 
@@ -198,12 +200,51 @@ def _bumped(sd, value: float, channel: int):
     return sd
 
 
-def regime(name: str, shape=COMPILED, kind: str = "diff", n: int = N) -> dict:
+ETA_NOISE = 0.5        # eta of the sampler cases that pass the caller's noise
+T_START = 34           # the hypothesis start's timestep: the first one the K = 3 sequence [0, 17, 34] executes
+START_ROWS = 3         # rows of the start's noise scale: pose n reads row n % 3 (fewer rows than poses)
+
+
+def start_xT(x, e, scale, t_start: int, b) -> torch.Tensor:
+    """x_T = x * a.sqrt() + (e * scale) * (1 - a).sqrt(), a = alpha_bar[t_start + 1] of the betas ``b``
+    (runners/diffpose_frame.py:355-363), in torch float32 on the CPU in the reference's order; pose n reads row
+    n % S of ``scale`` [S,J,5].  The two square roots are the float64 root rounded once to float32, which is the
+    correctly rounded sqrtf the library takes on the host (torch's float32 sqrt is not that on every CPU)."""
+    a = torch.from_numpy(alpha_bar_table(b.numpy()))[t_start + 1].view(1, 1, 1)
+    root = lambda v: torch.tensor(math.sqrt(float(v)), dtype=torch.float32).view(1, 1, 1)  # noqa: E731
+    e = e * scale.repeat(x.shape[0] // scale.shape[0], 1, 1)
+    return x * root(a) + e * root(1.0 - a)
+
+
+def regime(name: str, shape=COMPILED, kind: str = "diff", n: int = N, noise: bool = False,
+           start: bool = False) -> dict:
     """One regime at a model shape: state_dict ``sd``, adjacency ``adj`` (float32 numpy), input
     ``x``, per-pose timesteps ``t`` of the eps case, key ``mask`` [1,1,J] bool, schedule ``betas`` and
     ``seq`` (K = 3).  ``shape`` is (hid, heads, layers, joints, edges) with coords [5,5] ([2,3] for
     kind "pose"), or carries the GCNdiff coords as a sixth entry; every regime but "forms" is defined on
-    n = 9 poses of 5 (2) channels."""
+    n = 9 poses of 5 (2) channels.
+    ``noise``: also ``eta`` = ETA_NOISE and the caller's draws ``noise`` [K,N,J,5] (else eta 0, noise None).
+    ``start``: also the hypothesis start at ``t_start`` = T_START with ``start_scale`` [START_ROWS,J,5] (u, v
+    entries != 1) and the draws ``start_noise`` [N,J,5], and ``x_T``, the torch expression the loop then starts
+    from (start_xT); without it x_T is x."""
+    r = _regime(name, shape, kind, n)
+    r.update(eta=0.0, noise=None, x_T=r["x"])
+    if noise or start:
+        assert kind == "diff"
+        g = torch.Generator().manual_seed(7000 + r["x"].shape[1])
+        z = torch.randn((len(r["seq"]),) + tuple(r["x"].shape), generator=g)
+        e = torch.randn(r["x"].shape, generator=g)
+        sc = torch.ones((START_ROWS,) + tuple(r["x"].shape[1:]))
+        sc[:, :, :2] = 0.25 + 2.0 * torch.rand((START_ROWS, r["x"].shape[1], 2), generator=g)
+        if noise:
+            r.update(eta=ETA_NOISE, noise=z)
+        if start:
+            assert r["x"].shape[0] % START_ROWS == 0
+            r.update(t_start=T_START, start_scale=sc, start_noise=e, x_T=start_xT(r["x"], e, sc, T_START, r["betas"]))
+    return r
+
+
+def _regime(name: str, shape, kind: str, n: int) -> dict:
     hid, heads, layers, npts, edges = shape[:5]
     coords = 5 if len(shape) == 5 else shape[5]
     kw = {} if shape == COMPILED else dict(hid=hid, n_layers=layers, n_pts=npts)
@@ -254,11 +295,13 @@ def _gap(a, b) -> float:
 
 
 @functools.lru_cache(maxsize=None)
-def diff_oracles(name: str, shape=COMPILED, n: int = N) -> dict:
+def diff_oracles(name: str, shape=COMPILED, n: int = N, noise: bool = False, start: bool = False) -> dict:
     """eps at the regime's per-pose t (T_EPS; FORM_T cycled for "forms") and the K=3 trajectory of a
-    regime from the float32 and the float64 oracle: {"eps" | "xs" | "x0s": (o32, o64, g)}.
-    Computed once per (regime, shape, n); do not modify."""
-    r = regime(name, shape, n=n)
+    regime from the float32 and the float64 oracle: {"eps" | "xs" | "x0s": (o32, o64, g)}.  With ``noise`` /
+    ``start`` the trajectory is the one of regime(..., noise, start): eta and the caller's draws, and the loop
+    started from the float32 x_T (eps stays the forward at x).
+    Computed once per (regime, shape, n, noise, start); do not modify."""
+    r = regime(name, shape, n=n, noise=noise, start=start)
     t = r["t"]
     out = {}
     for dt in (torch.float32, torch.float64):
@@ -266,7 +309,8 @@ def diff_oracles(name: str, shape=COMPILED, n: int = N) -> dict:
         fwd = lambda a, mk, tt: O.gcndiff_forward(P, g, a, mk, tt, n_layers=r["layers"], heads=r["heads"])  # noqa: E731
         with torch.no_grad():
             eps = fwd(r["x"].to(dt), r["mask"], t)
-            xs, x0s = O.generalized_steps(r["x"].to(dt), r["mask"], r["seq"], fwd, r["betas"].to(dt))
+            xs, x0s = O.generalized_steps(r["x_T"].to(dt), r["mask"], r["seq"], fwd, r["betas"].to(dt), eta=r["eta"],
+                                          noise=None if r["noise"] is None else r["noise"].to(dt))
         out[dt] = {"eps": eps, "xs": torch.stack(xs), "x0s": torch.stack(x0s)}
     return {k: (out[torch.float32][k], out[torch.float64][k], _gap(out[torch.float32][k], out[torch.float64][k]))
             for k in ("eps", "xs", "x0s")}

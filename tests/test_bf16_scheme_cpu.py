@@ -7,7 +7,8 @@ runs, with S(a, b) the median over poses of the per-pose max |a - b| and ref = f
   own      max |ref - fp32 oracle|.
 Asserted per case: nearest / noise >= 100; own > 0 (another arithmetic than the oracle's); no noise variant has
 more than half of its poses beyond sqrt(noise x nearest); and the literal bar of the GPU file lies within
-[10 noise, nearest / 10].  The figures are printed (pytest -s).
+[10 noise, nearest / 10].  The figures are printed (pytest -s).  The cases tests/sampler_cells.py adds for the
+kernel table (bf16_scheme.KERNEL_CASES) are re-measured under the same conditions, with their bars there.
 
 sample/K2 is the exception the two-step cascade makes: a pose that met a rounding flip in the first evaluation
 enters the second with another input, so about 45 % of the poses of the 1e-6 variant are off and its median
@@ -58,6 +59,28 @@ def test_bar_separates_the_scheme_from_its_neighbours(name):
     for (case, d), why in B.BLIND.items():
         if case == name:
             assert 0.0 < dep[d] < 100.0 * noise, (d, dep[d], why)
+
+
+@pytest.mark.parametrize("name", B.KERNEL_CASES)
+def test_kernel_table_cases_are_remeasured(name):
+    """The cases tests/sampler_cells.py adds for the bf16 kernels no case above reaches (bf16_scheme.KERNEL_CASES):
+    one with a bar (BF16_BARS) meets the conditions above (the two-step sample/K2 cases those of sample/K2); one
+    recorded as dropped (BF16_DROPPED) still has no bar, like the dropped regimes below."""
+    from sampler_cells import BF16_BARS, BF16_DROPPED, BF16_NEED
+
+    noise, nearest, own, beyond, _ = B.figures(name)
+    need = BF16_NEED.get(name, RATIO["sample/K2"])
+    print(f"{name}: noise {noise:.3e}  nearest {nearest:.3e}  ratio {nearest / noise:.1f}  need {need:.0f}  own {own:.3e}  "
+          f"noise poses beyond sqrt(noise nearest) {beyond:.2f}")
+    assert own > 0.0
+    assert (name in BF16_BARS) != (name in BF16_DROPPED)
+    if name in BF16_DROPPED:
+        assert nearest / noise < need       # once this fails the case belongs in sampler_cells.BF16_BARS
+        return
+    assert nearest / noise >= need
+    assert beyond <= 0.5
+    m = math.sqrt(need)
+    assert m * noise <= BF16_BARS[name][0] <= nearest / m
 
 
 @pytest.mark.parametrize("regime", sorted(B.DROPPED_REGIMES))
