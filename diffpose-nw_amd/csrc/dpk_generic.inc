@@ -623,6 +623,43 @@ __global__ void __launch_bounds__(256) qsample(const float* x, float* xT, float*
     if (xT2) xT2[i] = v;
 }
 
+// ... at one timestep per pose (dpk_diff_loss; runners/diffpose_frame.py:216-222): pose p's roots are row t[p] of
+// the schedule's table qtab [nt][2] = (sqrtf(abar[t+1]), sqrtf(1 - abar[t+1])), the index clamped to the table (a NaN
+// compares false both times and reads row 0)
+__global__ void __launch_bounds__(256) qsample_t(const float* __restrict__ x, float* __restrict__ xT, long long n,
+                                                 int pe, const float* __restrict__ t, const float* __restrict__ qtab,
+                                                 int nt, const float* __restrict__ scale, int rows,
+                                                 const float* __restrict__ noise, unsigned long long seed) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int pose = (int)(i / pe);
+    const float tf = t[pose];
+    const int ti = tf >= 0.f ? (tf < (float)(nt - 1) ? (int)tf : nt - 1) : 0;
+    xT[i] = dpk::qsample_at(x[i], pose, (int)(i - (long long)pose * pe), pe, qtab[2 * ti], qtab[2 * ti + 1], scale, rows,
+                            noise, seed);
+}
+
+// The denoising objective per pose (runners/diffpose_frame.py:226, before the batch mean): one thread per pose adds
+// (target - eps)^2 over the pose's pe elements in ascending order into one fp32 accumulator; target = e * scale is
+// the product qsample_at noised x with (the same draws, the same scale row)
+__global__ void __launch_bounds__(256) diff_loss(const float* __restrict__ eps, int N, int pe,
+                                                 const float* __restrict__ scale, int rows,
+                                                 const float* __restrict__ noise, unsigned long long seed,
+                                                 float* __restrict__ loss) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= N) return;
+    const float* sc = scale ? scale + (size_t)(p % rows) * pe : nullptr;
+    float acc = 0.f;
+    for (int r = 0; r < pe; ++r) {
+        const long long g = (long long)p * pe + r;
+        const float e = noise ? noise[g] : dpk::normal_noise(seed, -1, g);
+        const float target = e * (sc ? sc[r] : 1.0f);
+        const float d = target - eps[g];
+        acc = acc + d * d;
+    }
+    loss[p] = acc;
+}
+
 // GCNpose's uvxyz assembly (runners/diffpose_frame.py:337-342) and xyz output, as dpk_pose's
 __global__ void __launch_bounds__(256) pose_out(const float* __restrict__ x2d, const float* __restrict__ y, int N,
                                                 int J, int cin, int cout, float* __restrict__ xyz,
@@ -1036,13 +1073,32 @@ static int gen_sample(dpk_handle* h, Sched* sc, const float* x, float* out, floa
     return rc ? rc : sched_note_use(h, sc, st, cap);
 }
 
-// dpk_eps on the generic path: per-pose timestep projections, one forward
-static int gen_eps(dpk_handle* h, const float* x, const float* t, float* eps, int N, hipStream_t st, bool cap) {
+// One dpkg::qsample_t launch over N poses of pe floats, and one dpkg::diff_loss launch over them (dpk_diff_loss)
+static void gen_qsample_t(hipStream_t st, const float* x, float* xT, int N, int pe, const float* t, const float* qtab,
+                          int nt, const StartSpec& s, uint64_t seed) {
+    const long long n = (long long)N * pe;
+    hipLaunchKernelGGL(dpkg::qsample_t, dim3(gen_blocks(n)), dim3(256), 0, st, x, xT, n, pe, t, qtab, nt, s.scale, s.rows,
+                       s.noise, (unsigned long long)seed);
+}
+static void gen_diff_loss(hipStream_t st, const float* eps, int N, int pe, const StartSpec& s, uint64_t seed,
+                          float* loss) {
+    hipLaunchKernelGGL(dpkg::diff_loss, dim3(gen_blocks(N)), dim3(256), 0, st, eps, N, pe, s.scale, s.rows, s.noise,
+                       (unsigned long long)seed, loss);
+}
+
+// floats of scratch one gen_eps call over N poses takes: the forward's activations, then the per-pose projections
+static size_t gen_eps_floats(const GenModel* g, int N) { return gen_act_floats(g, N) + (size_t)N * g->s.L * g->s.D; }
+
+// dpk_eps on the generic path: per-pose timestep projections, one forward.  S: gen_eps_floats(N) floats of the
+// call's scratch, or null to take them here
+static int gen_eps(dpk_handle* h, const float* x, const float* t, float* eps, int N, hipStream_t st, bool cap,
+                   float* S = nullptr) {
     GenModel* g = h->gen;
     const size_t act = gen_act_floats(g, N);
-    float* S = nullptr;
-    const int rc = gen_scratch(h, st, cap, act + (size_t)N * g->s.L * g->s.D, &S, "dpk_eps");
-    if (rc) return rc;
+    if (!S) {
+        const int rc = gen_scratch(h, st, cap, gen_eps_floats(g, N), &S, "dpk_eps");
+        if (rc) return rc;
+    }
     float* tproj = S + act;
     return profiled(h, st, cap, "dpk_eps", [&]() -> int {
         gen_temb(g, st, t, 1, N, tproj);

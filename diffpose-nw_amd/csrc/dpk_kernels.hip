@@ -114,6 +114,15 @@ struct SampleArgs {
     // [..][n_pts][5]).  In the padding ahead of the next pointer: no other field's offset moves
     int n_pts;
     const float* start_noise;   // [N][17][5] the caller's draws e, or null: normal_noise(seed, -1, element)
+    // The denoising loss (dpk_diff_loss; eps mode, read under if constexpr (EPS_MODE) alone; at the end, so no
+    // other field's offset moves).  With loss_t set the tile's load of x_in gives x_t = qsample_elem at pose n's own
+    // row clamp(loss_t[n]) of loss_qtab (scale, draws and seed are the start's fields above) and writes it to
+    // loss_xt; the epilogue stages (e*scale - eps)^2 and one lane per pose sums it into loss_out.  x_out may be null
+    const float* loss_t;        // [N] per-pose timesteps, or null: plain dpk_eps
+    const float* loss_qtab;     // [loss_nt][2] = sqrtf(abar[t + 1]), sqrtf(1 - abar[t + 1]) (Sched::qtab)
+    int loss_nt;
+    float* loss_out;            // [N] or null
+    float* loss_xt;             // [N][17][5] or null
 #if DPK_TRACE
     unsigned long long* trace;   // [blocks][NW][TRACE_SLOTS]
     int trace_step;
@@ -270,12 +279,15 @@ using namespace dpk;
 // passed its last launch (an event per stream), or never if a graph was captured with it.
 struct Sched {
     uint64_t serial = 0;           // unique per schedule built (keys the generic path's loop graphs)
-    float* buf = nullptr;          // device: coef, then tps (16-byte aligned)
+    float* buf = nullptr;          // device: coef, then tps (16-byte aligned), then qtab
     float* coef = nullptr;
     float* tps = nullptr;
+    float* qtab = nullptr;         // device: the noising roots [nt][2] (sched_roots), behind tps
+    int nt = 0;                    // timesteps of the alpha table: n_alpha - 1
     int K = 0;
     float eta = 0.f;
     std::vector<float> h_coef;
+    std::vector<float> h_qtab;     // qtab on the host (start_spec reads it)
     uint64_t tps_gen = 0;          // weights generation tps was computed from (0: not yet)
     int pins = 0;                  // captured graphs that read it (CapRes): kept while any is alive
     std::vector<std::pair<hipStream_t, hipEvent_t>> uses;   // last launch on each stream
@@ -336,7 +348,6 @@ struct dpk_handle {
     hipStream_t aux = nullptr;     // handle-internal stream for schedule construction
     uint64_t weights_gen = 0;      // bumped by every weight/graph upload
     Sched* sched = nullptr;        // current schedule
-    std::vector<float> abar;       // the alpha_bar table of the last dpk_set_schedule (the hypothesis start's a)
     std::vector<Sched*> retired;   // replaced schedules not yet known to be unused
     ScratchPool pool;              // timestep projections of dpk_eps (and dpk_sample, !sched_tps) or per-op scratch
     Stage stage;                   // host staging of the weights and the graph, whatever the shape
@@ -833,8 +844,10 @@ constexpr bool instances_consistent() {
 }
 static_assert(instances_consistent(), "an instance's fits and its compiled kernel modes disagree");
 
-// Scratch for dpk_eps's per-pose projections [N][NL][D].  Where the schedule holds dpk_sample's they are all the
-// pool serves: at least 64 poses, refusals in poses.  Elsewhere it is counted in floats (gen_scratch).
+// Scratch for dpk_eps's per-pose projections [N][NL][D] (dpk_diff_loss on an instance takes the same).  Where the
+// schedule holds dpk_sample's they are all the pool serves: at least 64 poses, refusals in poses (but for the
+// three-launch A/B form of dpk_diff_loss, DPK_LOSS_FUSED=0, which asks in floats).  Elsewhere it is counted in floats
+// (gen_scratch).
 static int eps_scratch(dpk_handle* h, hipStream_t st, bool cap, int N, float** out) {
     const size_t PP = h->w.inst->tp;
     if (!sched_tps(h)) return gen_scratch(h, st, cap, (size_t)N * PP, out, "dpk_eps");
@@ -1035,6 +1048,22 @@ int dpk_load_weights(dpk_handle* h, const char* const* names, const float* const
     return DPK_OK;
 }
 
+// The roots every noising reads, per timestep t of the alpha table: q[t] = (sqrtf(abar[t + 1]), sqrtf(1 - abar[t + 1])),
+// fp32 like the reference's a.sqrt() and (1.0 - a).sqrt() (runners/diffpose_frame.py:222, :363).  The one place
+// they are rounded: the hypothesis start at t_start (start_spec) and dpk_diff_loss's per-pose t read this table
+static std::vector<float> sched_roots(const float* abar, int n_alpha) {
+    std::vector<float> q((size_t)(n_alpha - 1) * 2);
+    for (int t = 0; t + 1 < n_alpha; ++t) {
+        const float a = abar[t + 1], one = 1.0f;
+        volatile float sa = sqrtf(a);
+        volatile float om = one - a;
+        volatile float sb = sqrtf(om);
+        q[2 * (size_t)t] = sa;
+        q[2 * (size_t)t + 1] = sb;
+    }
+    return q;
+}
+
 int dpk_set_schedule(dpk_handle* h, const float* abar, int n_alpha, const int* seq, int K, float eta) {
     if (!h || !abar || !seq || K <= 0 || n_alpha < 2) return fail(h, DPK_E_INVALID, "dpk_set_schedule: bad args");
     if (h->kind != 0) return fail(h, DPK_E_STATE, "GCNpose handle (coords 2->3) has no diffusion schedule");
@@ -1067,14 +1096,16 @@ int dpk_set_schedule(dpk_handle* h, const float* abar, int n_alpha, const int* s
     }
     HIPCHK(h, hipSetDevice(h->device));
     sched_sweep(h);
-    h->abar.assign(abar, abar + n_alpha);
+    const std::vector<float> q = sched_roots(abar, n_alpha);
     // an identical schedule keeps its device buffers (and every graph captured with them)
-    if (h->sched && h->sched->K == K && h->sched->eta == eta && h->sched->h_coef == c) return DPK_OK;
+    if (h->sched && h->sched->K == K && h->sched->eta == eta && h->sched->h_coef == c && h->sched->h_qtab == q)
+        return DPK_OK;
     Sched* s = new Sched();
     static uint64_t sched_serial = 0;
     s->serial = ++sched_serial;
     const size_t tps_off = ((size_t)K * 6 + 3) / 4 * 4;
-    hipError_t e = hipMalloc(&s->buf, (tps_off + (size_t)K * NL * D) * 4);
+    const size_t q_off = tps_off + (size_t)K * NL * D;
+    hipError_t e = hipMalloc(&s->buf, (q_off + q.size()) * 4);
     if (e != hipSuccess) {
         delete s;
         return fail(h, DPK_E_HIP, std::string("dpk_set_schedule: hipMalloc: ") + hipGetErrorString(e) +
@@ -1082,11 +1113,15 @@ int dpk_set_schedule(dpk_handle* h, const float* abar, int n_alpha, const int* s
     }
     s->coef = s->buf;
     s->tps = s->buf + tps_off;
+    s->qtab = s->buf + q_off;
+    s->nt = n_alpha - 1;
+    s->h_qtab = q;
     s->K = K;
     s->eta = eta;
     s->h_coef = c;
     // a fresh buffer no launch has seen: the copy cannot race any stream
     e = hipMemcpyAsync(s->coef, c.data(), c.size() * 4, hipMemcpyHostToDevice, h->aux);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->qtab, s->h_qtab.data(), q.size() * 4, hipMemcpyHostToDevice, h->aux);
     if (e == hipSuccess) e = hipStreamSynchronize(h->aux);
     if (e != hipSuccess) {
         sched_free(s);
@@ -1128,6 +1163,16 @@ static int check_ready(dpk_handle* h, int kind = 0) {
     return DPK_OK;
 }
 
+// dpk_eps on a sampler instance once its projection rows tp [N][NL][D] are there: the timestep MLP, then the tiles
+static int eps_launch(dpk_handle* h, const float* x, const float* t, float* eps, int N, hipStream_t st, bool cap,
+                      float* tp) {
+    h->w.inst->temb(h->w.temb, t, 1, N, tp, st);
+    HIPCHK(h, hipGetLastError());
+    return profiled(h, st, cap, "dpk_eps", [&] {
+        return launch_sampler(h, M_EPS, st, eps_args(h, h->w.arena, tp, x, eps, N), cap);
+    });
+}
+
 int dpk_eps(dpk_handle* h, const float* x, const float* t, float* eps, int N, void* stream) {
     if (!h) return DPK_E_INVALID;
     if (N < 0 || (N > 0 && (!x || !t || !eps))) return fail(h, DPK_E_INVALID, "dpk_eps: bad args");
@@ -1140,11 +1185,7 @@ int dpk_eps(dpk_handle* h, const float* x, const float* t, float* eps, int N, vo
     if (h->gen) return gen_eps(h, x, t, eps, N, st, cap);
     float* tp = nullptr;             // per-pose projections [N][NL][D]
     if ((rc = eps_scratch(h, st, cap, N, &tp))) return rc;
-    h->w.inst->temb(h->w.temb, t, 1, N, tp, st);
-    HIPCHK(h, hipGetLastError());
-    return profiled(h, st, cap, "dpk_eps", [&] {
-        return launch_sampler(h, M_EPS, st, eps_args(h, h->w.arena, tp, x, eps, N), cap);
-    });
+    return eps_launch(h, x, t, eps, N, st, cap, tp);
 }
 
 int dpk_sample(dpk_handle* h, const float* x, float* out, float* xs, float* x0s, int N, uint64_t seed,
@@ -1152,22 +1193,26 @@ int dpk_sample(dpk_handle* h, const float* x, float* out, float* xs, float* x0s,
     return dpk_sample_noise(h, x, out, xs, x0s, N, seed, nullptr, stream);
 }
 
-// The scalars of a hypothesis start at t_start from the handle's alpha_bar table, fp32 like the reference's
-// a.sqrt() and (1.0 - a).sqrt() (runners/diffpose_frame.py:363)
-static int start_spec(dpk_handle* h, const char* who, int N, int t_start, const float* scale, int scale_rows,
-                      const float* start_noise, StartSpec* s) {
-    if (h->abar.empty() || !h->sched) return fail(h, DPK_E_INVALID, std::string(who) + ": no schedule set (dpk_set_schedule)");
-    if ((size_t)t_start + 1 >= h->abar.size())
-        return fail(h, DPK_E_INVALID, std::string(who) + ": t_start " + std::to_string(t_start) + " outside the alpha table (index t_start + 1 of " +
-                                          std::to_string(h->abar.size()) + " entries)");
+// What every noising call checks first: a schedule is bound (its table of roots), and the scale rows divide the batch
+static int noising_check(dpk_handle* h, const char* who, int N, const float* scale, int scale_rows) {
+    if (!h->sched) return fail(h, DPK_E_INVALID, std::string(who) + ": no schedule set (dpk_set_schedule)");
     if (scale && (scale_rows < 1 || N % scale_rows != 0))
         return fail(h, DPK_E_INVALID, std::string(who) + ": scale_rows " + std::to_string(scale_rows) + " must be at least 1 and divide N = " +
                                           std::to_string(N));
-    const float a = h->abar[(size_t)t_start + 1], one = 1.0f;
-    volatile float sa = sqrtf(a);
-    volatile float om = one - a;
-    volatile float sb = sqrtf(om);
-    *s = StartSpec{sa, sb, scale, scale ? scale_rows : 1, start_noise};
+    return DPK_OK;
+}
+
+// The scalars of a hypothesis start at t_start: row t_start of the schedule's table of roots (sched_roots)
+static int start_spec(dpk_handle* h, const char* who, int N, int t_start, const float* scale, int scale_rows,
+                      const float* start_noise, StartSpec* s) {
+    if (!h->sched) return noising_check(h, who, N, scale, scale_rows);
+    if (t_start + 1 > h->sched->nt)
+        return fail(h, DPK_E_INVALID, std::string(who) + ": t_start " + std::to_string(t_start) + " outside the alpha table (index t_start + 1 of " +
+                                          std::to_string(h->sched->nt + 1) + " entries)");
+    const int rc = noising_check(h, who, N, scale, scale_rows);
+    if (rc) return rc;
+    const float* q = h->sched->h_qtab.data() + 2 * (size_t)t_start;
+    *s = StartSpec{q[0], q[1], scale, scale ? scale_rows : 1, start_noise};
     return DPK_OK;
 }
 
@@ -1245,6 +1290,70 @@ int dpk_q_sample(dpk_handle* h, const float* x, float* xT, int N, int t_start, c
     gen_qsample(st, x, xT, nullptr, N, h->gen ? h->gen->s.J * h->gen->s.cin : h->n_pts * CIN, start, seed);
     HIPCHK(h, hipGetLastError());
     return DPK_OK;
+}
+
+int dpk_diff_loss(dpk_handle* h, const float* x0, const float* t, const float* scale, int scale_rows,
+                  const float* noise, uint64_t seed, float* loss, float* xt, float* eps, int N, void* stream) {
+    if (!h) return DPK_E_INVALID;
+    if (N < 0 || (N > 0 && (!x0 || !t))) return fail(h, DPK_E_INVALID, "dpk_diff_loss: bad args");
+    if (!loss && !xt && !eps) return fail(h, DPK_E_INVALID, "dpk_diff_loss: loss_dev, xt_dev and eps_dev are all null");
+    if (h->kind != 0)
+        return fail(h, DPK_E_UNSUPPORTED, "dpk_diff_loss: GCNpose handle (coords 2->3) has no diffusion objective");
+    int rc = noising_check(h, "dpk_diff_loss", N, scale, scale_rows);
+    if (rc) return rc;
+    const bool need_eps = loss || eps;          // x_t alone needs neither weights nor a graph, like dpk_q_sample
+    if (need_eps && (rc = check_ready(h))) return rc;
+    if (N == 0) return DPK_OK;
+    Sched* sc = h->sched;
+    hipStream_t st = (hipStream_t)stream;
+    bool cap = false;
+    if ((rc = enter_call(h, N, "dpk_diff_loss", st, &cap))) return rc;
+    if (!cap) sched_sweep(h);
+    // A sampler instance runs it in dpk_eps's own launch: the noising where the tile loads its poses, the sum in the
+    // epilogue (sample_kernel, EPS_MODE).  DPK_LOSS_FUSED=0 keeps the three launches below on such a handle too (A/B)
+    const char* lf = getenv("DPK_LOSS_FUSED");
+    if (h->w.inst && need_eps && !(lf && atoi(lf) == 0)) {
+        float* tp = nullptr;
+        if ((rc = eps_scratch(h, st, cap, N, &tp))) return rc;
+        h->w.inst->temb(h->w.temb, t, 1, N, tp, st);
+        HIPCHK(h, hipGetLastError());
+        SampleArgs a = eps_args(h, h->w.arena, tp, x0, eps, N);
+        a.loss_t = t;
+        a.loss_qtab = sc->qtab;
+        a.loss_nt = sc->nt;
+        a.loss_out = loss;
+        a.loss_xt = xt;
+        a.start_scale = scale;
+        a.start_scale_rows = scale ? scale_rows : 1;
+        a.start_noise = noise;
+        a.seed = seed;
+        rc = profiled(h, st, cap, "dpk_diff_loss", [&] { return launch_sampler(h, M_EPS, st, a, cap); });
+        return rc ? rc : sched_note_use(h, sc, st, cap);
+    }
+    // one request of the call's scratch, counted in floats on every handle: what the eps evaluation takes (the
+    // per-op forward's buffers, or an instance's projection rows), then x_t and eps where the caller keeps neither
+    const int pe = h->gen ? h->gen->s.J * h->gen->s.cin : h->n_pts * CIN;
+    const auto up64 = [](size_t v) { return (v + 63) / 64 * 64; };   // 256-byte boundaries between the parts
+    const size_t n = (size_t)N * pe;
+    const size_t eps_floats = up64(!need_eps ? 0 : h->gen ? gen_eps_floats(h->gen, N) : (size_t)N * h->w.inst->tp);
+    const size_t extra = (xt ? 0 : up64(n)) + (need_eps && !eps ? n : 0);
+    float* S = nullptr;
+    if (eps_floats + extra && (rc = gen_scratch(h, st, cap, eps_floats + extra, &S, "dpk_diff_loss"))) return rc;
+    float* own = S ? S + eps_floats : nullptr;
+    if (!xt) xt = own, own += up64(n);
+    if (need_eps && !eps) eps = own;
+    const StartSpec spec{0.f, 0.f, scale, scale ? scale_rows : 1, noise};
+    gen_qsample_t(st, x0, xt, N, pe, t, sc->qtab, sc->nt, spec, seed);
+    HIPCHK(h, hipGetLastError());
+    if (need_eps) {
+        rc = h->gen ? gen_eps(h, xt, t, eps, N, st, cap, S) : eps_launch(h, xt, t, eps, N, st, cap, S);
+        if (rc) return rc;
+    }
+    if (loss) {
+        gen_diff_loss(st, eps, N, pe, spec, seed, loss);
+        HIPCHK(h, hipGetLastError());
+    }
+    return sched_note_use(h, sc, st, cap);
 }
 
 int dpk_pose(dpk_handle* h, const float* x2d, float* xyz, float* uvxyz, int N, int H, int root_mode,

@@ -2285,7 +2285,29 @@ __global__ void __launch_bounds__(NT, 1) sample_kernel(SampleArgs a, const float
                 }
             }
         }
-        if (PAD && START && start) {
+        bool noised = false;   // block-uniform: this load gave x_t of the denoising loss (eps mode, dpk_diff_loss)
+        if constexpr (EPS_MODE) {
+            if (a.loss_t) {
+                // x_t of the tile's live rows at each pose's own timestep: row clamp(t) of the schedule's roots (a
+                // NaN compares false both times and reads row 0); the PAD and the 17-joint forms of START's load
+                for (int i = tid; i < R * CIN; i += NT) {
+                    float v = 0.f;
+                    if (PAD ? live(i) : i < nvalid) {
+                        const int p = i / PE, pose = pose0 + p;
+                        const size_t g = PAD ? gmap(i) : (size_t)pose0 * PE + i;
+                        const float tf = a.loss_t[pose];
+                        const int ti = tf >= 0.f ? (tf < (float)(a.loss_nt - 1) ? (int)tf : a.loss_nt - 1) : 0;
+                        v = qsample_at(a.x_in[g], pose, i - p * PE, pe, a.loss_qtab[2 * ti], a.loss_qtab[2 * ti + 1],
+                                       a.start_scale, a.start_scale_rows, a.start_noise, a.seed);
+                        if (a.loss_xt) a.loss_xt[g] = v;
+                    }
+                    XST[i] = v;
+                }
+                noised = true;
+            }
+        }
+        if (noised) {
+        } else if (PAD && START && start) {
             for (int i = tid; i < R * CIN; i += NT) {
                 float v = 0.f;
                 if (live(i)) {
@@ -2600,7 +2622,19 @@ __global__ void __launch_bounds__(NT, 1) sample_kernel(SampleArgs a, const float
                 if (POSE) {
                     B1[r * LDX + c] = et;
                 } else if (EPS_MODE) {
-                    if (valid) a.x_out[gidx] = et;
+                    if (valid && a.x_out) a.x_out[gidx] = et;
+                    if (a.loss_out) {
+                        // fl(d * d), d = target - eps, staged in B1 (free in eps mode) at the pose state's index;
+                        // target = e * scale from the arrays x_t was noised with: the same product
+                        float dd = 0.f;
+                        if (valid) {
+                            const float e = a.start_noise ? a.start_noise[gidx] : normal_noise(a.seed, -1, (long long)gidx);
+                            const float sc = a.start_scale ? a.start_scale[(size_t)((pose0 + p) % a.start_scale_rows) * pe + (oidx - p * PE)] : 1.0f;
+                            const float d = e * sc - et;
+                            dd = d * d;
+                        }
+                        B1[oidx] = dd;
+                    }
                 } else {
                     // c1 * z: the caller's per-step draws (the reference's randn_like, utils_diff.py:65)
                     // or counter-based noise
@@ -2651,6 +2685,15 @@ __global__ void __launch_bounds__(NT, 1) sample_kernel(SampleArgs a, const float
                 }
                 for (int hh = 0; hh < a.H; ++hh) a.uvxyz[((size_t)hh * a.N + pose0) * PE + i] = v;
             }
+    } else {
+        // the denoising loss (after the epilogue's barrier): one lane per valid pose adds its n_pts * 5 staged
+        // squares in ascending element order into one accumulator
+        if (a.loss_out && tid < npose) {
+            const float* sq = B1 + tid * PE;
+            float acc = 0.f;
+            for (int i = 0; i < pe; ++i) acc = acc + sq[i];
+            a.loss_out[pose0 + tid] = acc;
+        }
     }
 }
 

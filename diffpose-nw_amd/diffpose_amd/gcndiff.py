@@ -338,7 +338,7 @@ class HipGCNdiff(_HipModel):
 
     __call__ = forward
 
-    def _check_start(self, x, t_start, start_scale, start_noise):
+    def _check_start(self, x, t_start, start_scale, start_noise, names=("start_scale", "start_noise")):
         """The hypothesis-start arguments of ``sample`` / ``q_sample`` for the batch x: (t_start, scale,
         scale rows, draws) with the tensors contiguous float32 on x's device, or None for no scale / draws."""
         t_start = int(t_start)
@@ -349,13 +349,13 @@ class HipGCNdiff(_HipModel):
         if start_scale is not None:
             if not (torch.is_tensor(start_scale) and start_scale.dtype == torch.float32 and start_scale.dim() == 3
                     and tuple(start_scale.shape[1:]) == pose and start_scale.device == x.device):
-                raise ValueError(f"start_scale must be a float32 tensor of shape (S,) + {pose} on {x.device}")
+                raise ValueError(f"{names[0]} must be a float32 tensor of shape (S,) + {pose} on {x.device}")
             start_scale = start_scale.contiguous()
             rows = start_scale.shape[0]
         if start_noise is not None:
             if not (torch.is_tensor(start_noise) and start_noise.dtype == torch.float32
                     and start_noise.shape == x.shape and start_noise.device == x.device):
-                raise ValueError(f"start_noise must be a float32 tensor of shape {tuple(x.shape)} on {x.device}")
+                raise ValueError(f"{names[1]} must be a float32 tensor of shape {tuple(x.shape)} on {x.device}")
             start_noise = start_noise.contiguous()
         return t_start, start_scale, rows, start_noise
 
@@ -430,6 +430,63 @@ class HipGCNdiff(_HipModel):
                                      ctypes.c_uint64(seed & (2**64 - 1)), stream)
         _lib.check(self._h, "dpk_q_sample", rc)
         return out
+
+    def _loss_timesteps(self, t, n: int, T: int):
+        """``t`` of ``diffusion_loss`` as the [n] float32 device array dpk_diff_loss takes.  Given on the CPU (a
+        list, numpy or a CPU tensor) it is checked: integer values in 0..T-1, else ValueError.  A device tensor is
+        passed on unchecked (no sync): integer values in that range are the caller's precondition, and the kernel
+        clamps the table index, so a bad value reads a wrong row, never outside the table."""
+        if torch.is_tensor(t) and t.is_cuda:
+            tt = t.to(device=self.device, dtype=torch.float32).reshape(-1)
+        else:
+            tc = torch.as_tensor(np.asarray(t.detach().numpy() if torch.is_tensor(t) else t)).reshape(-1)
+            tf = tc.to(torch.float64)
+            if tc.numel() and not bool(((tf == tf.round()) & (tf >= 0) & (tf <= T - 1)).all()):
+                raise ValueError(f"t must hold integer timesteps in 0..{T - 1}, got {tc.tolist()}")
+            tt = tf.to(torch.float32).to(self.device)
+        if tt.numel() == 1 and n != 1:
+            tt = tt.expand(n)
+        if tt.numel() != n:
+            raise ValueError(f"t must have {n} entries, got {tt.numel()}")
+        return tt.contiguous()
+
+    def diffusion_loss(self, x0, t, betas, noise_scale=None, noise=None, seed: int = 0, mask=None,
+                       return_parts: bool = False):
+        """The denoising loss per pose, the forward of the reference's training objective in eval mode
+        (runners/diffpose_frame.py:211-226, dropout off): ``x_t = x0 * a.sqrt() + (e * noise_scale) * (1 - a).sqrt()``
+        with ``a`` the alpha-bar of each pose's own timestep ``t[n]``, ``eps = model(x_t, mask, t)`` and
+        ``loss[n] = (e * noise_scale - eps).square().sum(dim=(1, 2))``, summed in ascending element order in fp32.
+        ``loss.mean()`` is the reference's ``loss_diff``.  Returns ``loss [N]``, or ``(loss, x_t, eps)`` with
+        ``return_parts``.
+
+        ``t``: [N] integer timesteps in 0..len(betas)-1 (``schedule.training_timesteps`` draws them as the
+        reference does); see ``_loss_timesteps`` for the check.  ``noise_scale``: [S,n_pts,5] with S dividing N (pose
+        n reads row n % S) or None (ones); ``noise``: the draws e, [N,n_pts,5], or None (counter-based from
+        ``seed``, the draws of ``q_sample``).  The bound schedule is kept, whatever its seq, when its betas are
+        ``betas``; otherwise ``([0], betas, 0.0)`` is bound.  At a uniform ``t`` the returned x_t is bitwise
+        ``q_sample(x0, t)``, and eps is bitwise ``model(x_t, mask, t)``."""
+        x0 = self._check_x(x0)
+        b = betas.detach().cpu().numpy() if torch.is_tensor(betas) else np.asarray(betas)
+        b = np.ascontiguousarray(b, dtype=np.float32)
+        if self._sched_key is None or self._sched_key[1] != b.tobytes():
+            self.set_schedule([0], b, 0.0)
+        n = x0.shape[0]
+        tt = self._loss_timesteps(t, n, b.shape[0])
+        _t0, sc, rows, e = self._check_start(x0, 0, noise_scale, noise, names=("noise_scale", "noise"))
+        self._sync_mask(mask)
+        self._check_mask_batch(n)
+        self._note_mask_use()
+        loss = torch.empty(n, dtype=torch.float32, device=self.device)
+        xt = torch.empty_like(x0) if return_parts else None
+        eps = torch.empty_like(x0) if return_parts else None
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = _lib.lib().dpk_diff_loss(self._h, x0.data_ptr(), tt.data_ptr(), sc.data_ptr() if sc is not None else None,
+                                      rows, e.data_ptr() if e is not None else None,
+                                      ctypes.c_uint64(seed & (2**64 - 1)), loss.data_ptr(),
+                                      xt.data_ptr() if xt is not None else None,
+                                      eps.data_ptr() if eps is not None else None, n, stream)
+        _lib.check(self._h, "dpk_diff_loss", rc)
+        return (loss, xt, eps) if return_parts else loss
 
     def ddim_update(self, xt, et, step: int, seed: int = 0, want_x0: bool = True, noise=None):
         """x_{t-1} (and x0) from an external eps for schedule step ``step``; ``noise``: this step's

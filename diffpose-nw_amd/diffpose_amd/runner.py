@@ -8,6 +8,7 @@ Mirrors ``Diffpose`` in ``runners/diffpose_frame.py``:
 | ``create_diffusion_model`` | 118-132 | ``HipGCNdiff`` handle, optional checkpoint |
 | ``create_pose_model`` | 134-154 | ``HipGCNpose`` handle, optional checkpoint |
 | ``test_hyber`` | 270-420 | pose front-end plus uvxyz assembly (one launch); the K-step DDIM sampler (one launch); per-frame MPJPE / P-MPJPE (one launch); the reference's per-action accounting on the host. Returns (p1, p2) in mm |
+| ``diffusion_loss`` | 203-233, forward only | the training objective in eval mode: per-pose-t noising, eps and the per-pose sums in one ``dpk_diff_loss`` call per batch; the reference's ``update(loss_diff, n)`` on the host. Returns the epoch average |
 
 Several ranks (``torch.distributed`` initialised with world size > 1, one process per GPU): every
 rank reads the same batches, takes the contiguous frame range ``shard_frames(B, world, rank)`` of
@@ -57,7 +58,7 @@ import torch
 import torch.distributed as dist
 
 from . import metrics
-from .data import shard_frames, synthetic_eval_batches
+from .data import shard_frames, synthetic_batch, synthetic_eval_batches
 from .dist import gather_frames, shard_rows
 from .gcndiff import H36M_EDGES, HipGCNdiff, adj_mx_from_edges
 from .gcnpose import HipGCNpose
@@ -324,6 +325,62 @@ class Diffpose:
             self.hypothesis_loss = {"best": (b1, b2), "mean": (m1, m2), "frames": self._hyp_frames}
         self.action_error_sum = err
         return metrics.print_error(None, err, is_train if rank == 0 else True)   # one table per job
+
+    def _pose_losses(self, x0, noise_scale, t, e, i):
+        """Per-pose denoising losses of one (shard of a) batch: one ``dpk_diff_loss`` call, float32 [F] on the device."""
+        if x0.shape[0] == 0:
+            return torch.empty(0, dtype=torch.float32, device=self.device)
+        dev = lambda a: torch.as_tensor(a, dtype=torch.float32).to(self.device)   # noqa: E731
+        return self.model_diff.diffusion_loss(dev(x0), t, self.betas, noise_scale=dev(noise_scale), noise=dev(e),
+                                              mask=self.src_mask)
+
+    def diffusion_loss(self, batches=None, n_frames: int = 4096, pose_losses=None):
+        """The validation value of the reference's training objective (runners/diffpose_frame.py:203-233 with the
+        model in eval mode: dropout off, no backward): for every batch ``(targets_uvxyz [B,n_pts,5], noise_scale
+        [B,n_pts,5], ...)`` — the leading two of what ``PoseGeneratorGMM.batch`` yields — draw ``t`` as ``:216-218``
+        (``schedule.training_timesteps``) and ``e`` as ``:214``, take ``loss_diff`` = the mean of the per-pose
+        losses (``HipGCNdiff.diffusion_loss``) and book ``update(loss_diff, B)`` as ``:233``; returns the epoch
+        average.  ``t`` and ``e`` come from one CPU generator seeded with ``args.seed``, drawn for the whole batch,
+        so the value does not depend on the world size: under a multi-rank torch.distributed job each rank runs
+        the poses ``shard_frames(B, world, rank)`` and one all-gather of the per-pose losses (4 B per pose) puts
+        them back in batch order, after which every rank books the same mean as one process would.  Without
+        ``batches``: seeded synthetic poses with noise scales in [0.5, 1.5).  ``pose_losses`` replaces the per-shard
+        compute (tests of the distributed accounting on CPU): ``fn(x0, noise_scale, t, e, batch_index) -> [F]``
+        float32 losses for the rank's F poses, ``t`` an int64 CPU tensor and ``e`` a float32 CPU tensor."""
+        from .schedule import training_timesteps
+
+        if batches is None:
+            x, _ = synthetic_batch(n_frames, seed=self.args.seed, num_pts=self.n_pts)
+            rng = np.random.Generator(np.random.PCG64(self.args.seed + 1))
+            scale = (0.5 + rng.random(size=x.shape)).astype(np.float32)
+            bs = int(self.config.training.batch_size)
+            batches = [(x[lo:lo + bs], scale[lo:lo + bs]) for lo in range(0, n_frames, bs)]
+        world, rank, distributed = self._world()
+        if pose_losses is None:
+            pose_losses = self._pose_losses
+            self.model_diff.eval()
+        gen = torch.Generator().manual_seed(int(self.args.seed))
+        epoch = metrics.AverageMeter()
+        with torch.no_grad():
+            for i, batch in enumerate(batches):
+                x0, noise_scale = batch[0], batch[1]
+                x0 = torch.as_tensor(x0).detach().to(torch.float32)
+                noise_scale = torch.as_tensor(noise_scale).detach().to(torch.float32)
+                B = x0.shape[0]
+                if tuple(x0.shape) != (B, self.n_pts, 5) or noise_scale.shape != x0.shape:
+                    raise ValueError(f"batch {i}: targets_uvxyz and noise_scale must be ({B}, {self.n_pts}, 5), got "
+                                     f"{tuple(x0.shape)} and {tuple(noise_scale.shape)}")
+                if B == 0:
+                    continue
+                e = torch.randn((B, self.n_pts, 5), generator=gen)             # :214, for the whole batch
+                t = training_timesteps(B, self.num_timesteps, generator=gen)   # :216-218
+                lo, hi = shard_frames(B, world, rank)
+                loss = pose_losses(x0[lo:hi], noise_scale[lo:hi], t[lo:hi], e[lo:hi], i).to(torch.float32)
+                if distributed:
+                    loss = gather_frames(loss.reshape(-1, 1), B, 1).reshape(-1)
+                epoch.update(float(loss.cpu().mean()), B)                      # :226's batch mean, :233
+        self.epoch_loss_diff = epoch.avg
+        return epoch.avg
 
     def log_performance_metrics(self, output_path=None):
         """Summary of the per-batch inference times and peak-memory deltas collected under

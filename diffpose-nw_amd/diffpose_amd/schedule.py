@@ -65,6 +65,20 @@ def make_seq(skip_type: str, test_num_diffusion_timesteps: int, test_timesteps: 
     raise NotImplementedError(skip_type)
 
 
+def training_timesteps(n: int, T: int, generator=None):
+    """The reference's antithetic timestep draw for a batch of n poses (runners/diffpose_frame.py:216-218):
+    ``t = randint(0, T, (n // 2 + 1,)); cat([t, T - t - 1])[:n]``, an int64 CPU tensor in 0..T-1 from torch's
+    default generator (or ``generator``), so the draws are the reference's under the same seed."""
+    import torch
+
+    n, T = int(n), int(T)
+    if generator is None:
+        t = torch.randint(low=0, high=T, size=(n // 2 + 1,))
+    else:
+        t = torch.randint(low=0, high=T, size=(n // 2 + 1,), generator=generator)
+    return torch.cat([t, T - t - 1], dim=0)[:n]
+
+
 def step_pairs(seq):
     """(t, next_t) in execution order (common/utils_diff.py:49-52)."""
     seq = list(seq)

@@ -112,6 +112,38 @@ def generalized_steps(x, src_mask, seq, model, b, **kwargs):
         return xs, x0s
 
 
+def diffusion_loss(model, x0, t, b, noise_scale=None, noise=None, mask=None, seed: int = 0,
+                   return_parts: bool = False):
+    """The per-pose denoising loss ``(e - model(x_t, mask, t)).square().sum(dim=(1, 2))`` of the reference's
+    training step in eval mode (runners/diffpose_frame.py:211-226), ``e = noise * noise_scale`` and
+    ``x_t = x0 * a.sqrt() + e * (1 - a).sqrt()`` at each pose's own timestep ``t[n]``; its mean is ``loss_diff``.
+
+    * ``model`` a :class:`HipGCNdiff` → one ``dpk_diff_loss`` call (``HipGCNdiff.diffusion_loss``); ``noise`` None
+      then means counter-based draws from ``seed``.
+    * any other callable ``model(xt, mask, t, cemd)`` → the reference's three lines in torch on x0's device, alpha-bar
+      from the fp32 host table (``compute_alpha``); ``noise`` None then draws ``torch.randn_like(x0)`` (:214).
+
+    ``noise_scale``: [S, n_pts, 5] with S dividing N (pose n reads row n % S) or None.  Returns ``loss [N]``, or
+    ``(loss, x_t, eps)`` with ``return_parts``."""
+    if isinstance(model, HipGCNdiff):
+        return model.diffusion_loss(x0, t, b, noise_scale=noise_scale, noise=noise, seed=seed, mask=mask,
+                                    return_parts=return_parts)
+    with torch.no_grad():
+        n = x0.size(0)
+        t = torch.as_tensor(t).reshape(-1).to(x0.device)
+        e = torch.randn_like(x0) if noise is None else noise.to(x0.device)
+        if noise_scale is not None:
+            scale = noise_scale.to(x0.device)
+            if scale.size(0) < 1 or n % scale.size(0) != 0:
+                raise ValueError(f"noise_scale has {scale.size(0)} rows, which must divide the batch of {n} poses")
+            e = e * scale.repeat(n // scale.size(0), 1, 1)
+        a = compute_alpha(b, t.long()).to(x0.device)
+        x = x0 * a.sqrt() + e * (1.0 - a).sqrt()
+        out = model(x, mask, t.float(), 0)
+        loss = (e - out).square().sum(dim=(1, 2))
+    return (loss, x, out) if return_parts else loss
+
+
 # One schedule-only DDIM handle per (device, thread), reused by every generic-callable call: the
 # reference's sampler allocates nothing persistent (common/utils_diff.py:46-68), so neither should
 # a call here (a handle costs dpk_create, device buffers and a schedule upload).  A handle serves one

@@ -190,6 +190,33 @@ int dpk_q_sample(dpk_handle* h, const float* x_dev, float* xT_dev, int N, int t_
                  const float* scale_dev, int scale_rows, const float* start_noise_dev,
                  uint64_t seed, void* stream);
 
+/* The forward of the training objective in eval mode (runners/diffpose_frame.py:211-226; dropout off): the
+ * denoising loss of N poses, each noised at its own timestep.  For pose n with t = t_dev[n] and element r:
+ *   target = e * scale                                    (the reference's e = e * targets_noise_scale)
+ *   x_t    = (x0 * sa[t]) + (target * sb[t])              (the four roundings of dpk_q_sample)
+ *   eps    = GCNdiff(x_t, mask, t)                         (bitwise dpk_eps of (x_t, t) on this handle)
+ *   loss_dev[n] = sum over r ascending of (target - eps)^2, one fp32 accumulator, no FMA
+ * with sa[t] = sqrtf(alpha_bar[t + 1]) and sb[t] = sqrtf(1 - alpha_bar[t + 1]) from the table built and uploaded
+ * with the schedule, the one dpk_q_sample and dpk_sample_start read: at t_dev == t_start everywhere x_t is bitwise
+ * dpk_q_sample's x_T.  The batch mean of loss_dev is the reference's loss_diff (:226).
+ *   x0_dev    [N,n_pts,5] the clean poses
+ *   t_dev     [N] float, integer-valued, 0 .. n_alpha - 2 (the array dpk_eps takes); the table index is clamped to
+ *             that range (NaN reads row 0), so no value reads outside the table
+ *   scale_dev [scale_rows,n_pts,5] or NULL (ones); pose n reads row n % scale_rows, which must divide N
+ *   noise_dev [N,n_pts,5] the draws e, or NULL: counter-based from `seed` at step -1 (the start's key)
+ *   loss_dev [N], xt_dev [N,n_pts,5], eps_dev [N,n_pts,5]: outputs, each optional, at least one non-NULL
+ * GCNdiff handles of every kind, every gemm mode the handle has, the handle's key mask and per-pose masks as in
+ * dpk_eps.  DPK_E_UNSUPPORTED on a GCNpose handle; DPK_E_INVALID with dpk_sample_start's wording when no schedule
+ * is set or scale_rows does not divide N.  On a handle with a persistent sampler instance (dpk_fused) it is dpk_eps's
+ * one launch: the noising where the eps-mode tile loads its poses, the sum in its epilogue (the squares staged in LDS,
+ * one lane per pose), nothing but the projection rows in scratch; DPK_LOSS_FUSED=0 runs the three-launch form there
+ * too (A/B).  Per op it is three launches (noising, the dpk_eps forward, the per-pose sums), with x_t and eps that the
+ * caller does not ask for in the call's scratch; x_t alone is the noising kernel on every handle.  Capture-safe like
+ * dpk_eps (make the same call once uncaptured first); a captured call keeps the schedule it was captured with. */
+int dpk_diff_loss(dpk_handle* h, const float* x0_dev, const float* t_dev, const float* scale_dev, int scale_rows,
+                  const float* noise_dev, uint64_t seed, float* loss_dev, float* xt_dev, float* eps_dev, int N,
+                  void* stream);
+
 /* One DDIM update for an externally computed eps (generic model callables):
  * the per-element body of common/utils_diff.py:59-65 for schedule step `step`
  * (0 = first executed step, t = seq[K-1]).  x0_out may be NULL. */
