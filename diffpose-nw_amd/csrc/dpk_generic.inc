@@ -1059,7 +1059,8 @@ static int gen_sample(dpk_handle* h, Sched* sc, const float* x, float* out, floa
             gen_qsample(st, x, state, xs, N, g->s.J * g->s.cin, *start, seed);
         } else {
             if (xs) HIPCHK(h, hipMemcpyAsync(xs, x, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
-            HIPCHK(h, hipMemcpyAsync(state, x, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+            // out_dev == x_dev (x = sample(x)) launched directly: the state is already in place
+            if (state != x) HIPCHK(h, hipMemcpyAsync(state, x, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
         }
         if (graphed) {
             HIPCHK(h, hipGraphLaunch(ex, st));

@@ -250,9 +250,10 @@ namespace dpk {
 
 // ---------------------------------------------------------------------------------------
 // Elementwise DDIM update for externally computed eps; z from the caller's draws of this step
-// (`noise`, n floats) or counter-based.
-__global__ void __launch_bounds__(256) ddim_kernel(const float* __restrict__ xt, const float* __restrict__ et,
-                                                   float* __restrict__ xn, float* __restrict__ x0o, long long n,
+// (`noise`, n floats) or counter-based.  xt and xn may be one array (a caller's x = update(x), as dpkg::ddim runs
+// the per-op loop): neither is __restrict__.
+__global__ void __launch_bounds__(256) ddim_kernel(const float* xt, const float* __restrict__ et,
+                                                   float* xn, float* __restrict__ x0o, long long n,
                                                    const float* __restrict__ cf, int step, float eta,
                                                    unsigned long long seed, const float* __restrict__ noise) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;

@@ -15,6 +15,14 @@
  *     on the device the handle was created for; work is enqueued on `stream`
  *     (a hipStream_t, NULL = default stream) and is asynchronous.
  *   - Poses are (N, n_pts, 5) uvxyz: N poses x the handle's joints (17 on Human3.6M) x 5 channels.
+ *   - Caller memory (tests/test_gpu_caller_memory.py holds every entry point to this, each array between guard
+ *     words): a call reads and writes exactly the extents documented for each array, not one element before or
+ *     past them, so an array may end at the last byte the caller owns.  float arrays (and the 32-bit mask
+ *     and status words) need 4-byte alignment and nothing more; double and int64 arrays their natural 8 bytes.  Inputs are never written.  Every element of a
+ *     non-NULL output is written; an optional output passed as NULL is not touched, and a call over N = 0 poses
+ *     (elements, frames) returns DPK_OK and touches nothing.  An output may BE an input only where its description
+ *     says "may be": the same pointer, the same extent.  Any other overlap between the arrays of one call is
+ *     undefined.
  *   - Return value 0 = OK, negative = error (DPK_E_*); dpk_last_error() has the text.
  *   - A handle is bound to one device and is not thread-safe: one handle per rank/thread.
  *   - Stream order: launches (dpk_sample / dpk_eps / dpk_pose / dpk_ddim_update) may be in
@@ -137,13 +145,14 @@ int dpk_set_pose_masks(dpk_handle* h, const uint32_t* bits_dev, int n);
 int dpk_set_schedule(dpk_handle* h, const float* alpha_bar, int n_alpha, const int* seq, int K, float eta);
 
 /* One denoiser evaluation eps = GCNdiff(x, mask, t) for N poses with a
- * per-pose timestep t_dev[N] (float, as model(xt, mask, t.float(), 0)). */
+ * per-pose timestep t_dev[N] (float, as model(xt, mask, t.float(), 0)).  eps_dev [N,n_pts,5] may be x_dev. */
 int dpk_eps(dpk_handle* h, const float* x_dev, const float* t_dev, float* eps_dev, int N, void* stream);
 
 /* The whole K-step reverse loop of generalized_steps for N poses in ONE
  * persistent kernel (the per-step timestep projections come with the schedule).
  *   x_dev   [N,n_pts,5] input x (= xs[0])
- *   out_dev [N,n_pts,5] final sample xs[-1]
+ *   out_dev [N,n_pts,5] final sample xs[-1]; may be x_dev (x = sample(x)), the step-split last round and the
+ *           hypothesis start of dpk_sample_start included: xs[0] still holds what the loop started from
  *   xs_dev  [K+1,N,n_pts,5] or NULL: full trajectory xs (xs[0] copied from x_dev; x_T under dpk_sample_start)
  *   x0s_dev [K,N,n_pts,5]   or NULL: x0_preds
  *   seed: noise stream for eta > 0 (counter-based, not torch.randn_like). */
@@ -219,7 +228,7 @@ int dpk_diff_loss(dpk_handle* h, const float* x0_dev, const float* t_dev, const 
 
 /* One DDIM update for an externally computed eps (generic model callables):
  * the per-element body of common/utils_diff.py:59-65 for schedule step `step`
- * (0 = first executed step, t = seq[K-1]).  x0_out may be NULL. */
+ * (0 = first executed step, t = seq[K-1]).  x0_dev may be NULL; xnext_dev may be xt_dev. */
 int dpk_ddim_update(dpk_handle* h, const float* xt_dev, const float* eps_dev, float* xnext_dev,
                     float* x0_dev, int64_t n_elems, int step, uint64_t seed, void* stream);
 
