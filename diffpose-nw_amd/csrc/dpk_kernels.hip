@@ -327,6 +327,7 @@ struct InstWeights {
 };
 
 struct GenModel;   // dpk_generic.inc: the per-op forward for model shapes no instance is compiled for
+struct BwdModel;   // dpk_generic_bwd.inc: what dpk_diff_loss_grad keeps (built on its first call)
 struct dpk_handle {
     int device = 0;
     GenModel* gen = nullptr;       // non-null: this handle's shape runs on the per-op path (then w.inst is null)
@@ -352,6 +353,8 @@ struct dpk_handle {
     std::vector<Sched*> retired;   // replaced schedules not yet known to be unused
     ScratchPool pool;              // timestep projections of dpk_eps (and dpk_sample, !sched_tps) or per-op scratch
     Stage stage;                   // host staging of the weights and the graph, whatever the shape
+    uint64_t stage_serial = 0;     // bumped whenever the staging is uploaded anew (pack_upload)
+    BwdModel* bwd = nullptr;       // dpk_diff_loss_grad's arenas (and, on a sampler instance, its per-op model)
     int gemm_mode = 0;             // 0: fp32 MFMA, 1: 3x fp16-split MFMA, 2: bf16 MFMA (dpk_set_gemm_mode)
     int tile_waves = 0;            // dpk_set_tile_waves: 4 or 8 waves on the 4-pose tiles of dpk_sample; 0 the mode's default
     bool have_graph = false, have_weights = false;
@@ -795,6 +798,8 @@ static SampleArgs pose_args(const dpk_handle* h, const float* arena, const float
 }
 
 #include "dpk_generic.inc"
+#include "dpk_grad_layout.inc"
+#include "dpk_generic_bwd.inc"
 
 // ---------------------------------------------------------------------------------------
 // The compiled sampler instances: which shapes have a fused kernel, on which tile, with which kernel modes.
@@ -883,7 +888,7 @@ static int enter_call(dpk_handle* h, int N, const char* who, hipStream_t st, boo
 
 extern "C" {
 
-int dpk_version(void) { return 101; }
+int dpk_version(void) { return 102; }
 
 int dpk_kernel_geometry(int* ppw, int* tpw, int* lds) {
     if (ppw) *ppw = P;
@@ -976,6 +981,7 @@ void dpk_destroy(dpk_handle* h) {
     if (h->tproj_zero) (void)hipFree(h->tproj_zero);
     if (h->flags) (void)hipFree(h->flags);
     gen_free(h->gen);
+    bwd_free(h->bwd);
     // hipFree waits for the device, so in-flight launches finish before their buffers go
     if (h->sched) sched_free(h->sched);
     for (Sched* s : h->retired) sched_free(s);
@@ -1001,6 +1007,7 @@ const char* dpk_last_error(const dpk_handle* h) { return h ? h->err.c_str() : "n
 // Repack the handle's arenas from its staging and upload them (weights loaded; the graph's terms are zeros
 // until dpk_set_graph).  Weights and graphs are loaded rarely, so everything is repacked every time.
 static int pack_upload(dpk_handle* h) {
+    ++h->stage_serial;
     if (h->gen) return gen_upload(h, h->gen);
     h->w.inst->pack(h->stage, h->w.pk, true);      // with the half-width arenas of the modes the instance has
     return upload(h);
@@ -1357,6 +1364,58 @@ int dpk_diff_loss(dpk_handle* h, const float* x0, const float* t, const float* s
     return sched_note_use(h, sc, st, cap);
 }
 
+int dpk_diff_loss_grad(dpk_handle* h, const float* x0, const float* t, const float* scale, int scale_rows,
+                       const float* noise, uint64_t seed, float weight, float* loss, float* grads, int N, void* stream) {
+    if (!h) return DPK_E_INVALID;
+    if (N < 0 || (N > 0 && (!x0 || !t || !grads))) return fail(h, DPK_E_INVALID, "dpk_diff_loss_grad: bad args");
+    if (h->kind != 0)
+        return fail(h, DPK_E_UNSUPPORTED, "dpk_diff_loss_grad: GCNpose handle (coords 2->3) has no diffusion objective");
+    if (h->gemm_mode != 0)
+        return fail(h, DPK_E_UNSUPPORTED, "dpk_diff_loss_grad: the backward is fp32 (per-op kernels on the fp32 MFMA); "
+                                          "set gemm mode 0 (fp32) for the call");
+    int rc = noising_check(h, "dpk_diff_loss_grad", N, scale, scale_rows);
+    if (rc) return rc;
+    if ((rc = check_ready(h))) return rc;
+    if (N == 0) return DPK_OK;
+    hipStream_t st = (hipStream_t)stream;
+    bool cap = false;
+    if ((rc = enter_call(h, N, "dpk_diff_loss_grad", st, &cap))) return rc;
+    if (cap)
+        return fail(h, DPK_E_STATE, "dpk_diff_loss_grad: not callable while a graph is being captured (its scratch and "
+                                    "its arenas are allocated by the call)");
+    sched_sweep(h);
+    if ((rc = bwd_prepare(h))) return rc;
+    const StartSpec spec{0.f, 0.f, scale, scale ? scale_rows : 1, noise};
+    if ((rc = bwd_run(h, x0, t, spec, seed, weight, loss, grads, N, st))) return rc;
+    return sched_note_use(h, h->sched, st, false);
+}
+
+int dpk_param_count(const dpk_handle* h) {
+    if (!h || h->kind != 0) return 0;
+    return (int)grad_layout(h->stage).e.size();
+}
+
+int dpk_param_layout(const dpk_handle* h, int i, const char** name, int64_t* offset, int64_t* numel) {
+    if (!h || h->kind != 0) return DPK_E_UNSUPPORTED;
+    // names live as long as the process: one table per shape ever asked for
+    static std::vector<std::pair<std::string, GradLayout>*> tables;
+    const Stage& s = h->stage;
+    const std::string key = std::to_string(s.D) + "/" + std::to_string(s.J) + "/" + std::to_string(s.L) + "/" +
+                            std::to_string(s.cin) + "/" + std::to_string(s.cout);
+    const GradLayout* g = nullptr;
+    for (auto* tb : tables)
+        if (tb->first == key) g = &tb->second;
+    if (!g) {
+        tables.push_back(new std::pair<std::string, GradLayout>(key, grad_layout(s)));
+        g = &tables.back()->second;
+    }
+    if (i < 0 || i >= (int)g->e.size()) return DPK_E_INVALID;
+    if (name) *name = g->e[i].name.c_str();
+    if (offset) *offset = g->e[i].offset;
+    if (numel) *numel = g->e[i].numel;
+    return DPK_OK;
+}
+
 int dpk_pose(dpk_handle* h, const float* x2d, float* xyz, float* uvxyz, int N, int H, int root_mode,
              void* stream) {
     if (!h) return DPK_E_INVALID;
@@ -1492,6 +1551,14 @@ int dpk_debug_resources(dpk_handle* h, int* out, int n) {
 int dpk_debug_generic_forms(dpk_handle* h, unsigned* forms) {
     if (!h || !forms) return DPK_E_INVALID;
     *forms = gen_take_forms(h->gen);
+    return DPK_OK;
+}
+
+int dpk_debug_grad_forms(dpk_handle* h, unsigned* gemm_forms, unsigned* bwd_forms) {
+    if (!h || !gemm_forms || !bwd_forms) return DPK_E_INVALID;
+    *gemm_forms = h->bwd ? h->bwd->fforms : 0;
+    *bwd_forms = h->bwd ? h->bwd->bforms : 0;
+    if (h->bwd) h->bwd->fforms = h->bwd->bforms = 0;
     return DPK_OK;
 }
 

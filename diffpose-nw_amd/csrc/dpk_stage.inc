@@ -22,6 +22,7 @@ struct Stage {
     size_t wtp = 0, btp = 0;   // every layer's temb_proj: [L][E][D] (k-major), [L][D]
     size_t floats = 0;
     std::vector<float> h;      // the arena (offsets above, each 16-byte aligned)
+    std::vector<float> ahat;   // every layer's A_hat as loaded, [L][J*J]: the gradient goes back through lg to it
 };
 
 // What a sampler instance's pack_model makes of a Stage: its weight arena and timestep-MLP arena in the
@@ -129,6 +130,7 @@ static bool stage_load(Stage& s, const char* const* names, const float* const* p
     err.clear();
     const int D = s.D, E = s.E, J = s.J;
     std::vector<float> fresh = s.h;     // keeps the graph's terms
+    std::vector<float> fresh_ahat((size_t)s.L * J * J);
     float* A = fresh.data();
     for (int l = 0; l < s.L; ++l) {
         const GenLayer& o = s.lay[l];
@@ -155,6 +157,7 @@ static bool stage_load(Stage& s, const char* const* names, const float* const* p
         const float* c2b = get(gc + "gconv2.gconv.bias", D);
         if (!ahat || !f1w || !f1b || !f2w || !f2b || !n0a || !n0b || !n1a || !n1b || !c1w || !c1b || !c2w || !c2b)
             return false;
+        std::copy(ahat, ahat + (size_t)J * J, fresh_ahat.begin() + (size_t)l * J * J);
         for (int k = 0; k < D; ++k)
             for (int n = 0; n < 3 * D; ++n) A[o.wqkv + (size_t)k * 3 * D + n] = w[n / D][(size_t)(n % D) * D + k];
         for (int n = 0; n < 3 * D; ++n) A[o.bqkv + n] = b[n / D][n % D];
@@ -214,5 +217,6 @@ static bool stage_load(Stage& s, const char* const* names, const float* const* p
         std::copy(d1b, d1b + E, A + s.d1b);
     }
     s.h.swap(fresh);
+    s.ahat.swap(fresh_ahat);
     return true;
 }

@@ -17,10 +17,10 @@ ERRORS = {-1: "DPK_E_INVALID", -2: "DPK_E_UNSUPPORTED", -3: "DPK_E_HIP", -4: "DP
 
 # every symbol include/diffpose_kernels.h declares
 EXPORTS = ("dpk_version", "dpk_create", "dpk_set_graph", "dpk_load_weights", "dpk_set_mask", "dpk_set_pose_masks",
-           "dpk_set_schedule", "dpk_eps", "dpk_sample", "dpk_sample_noise", "dpk_sample_start", "dpk_q_sample", "dpk_diff_loss", "dpk_ddim_update", "dpk_ddim_update_noise",
+           "dpk_set_schedule", "dpk_eps", "dpk_sample", "dpk_sample_noise", "dpk_sample_start", "dpk_q_sample", "dpk_diff_loss", "dpk_diff_loss_grad", "dpk_param_count", "dpk_param_layout", "dpk_ddim_update", "dpk_ddim_update_noise",
            "dpk_pose", "dpk_pose_metrics", "dpk_pose_metrics_n", "dpk_gmm_sample", "dpk_gmm_sample_f64", "dpk_gmm_sample_n",
            "dpk_gmm_sample_f64_n", "dpk_set_gemm_mode", "dpk_gemm_modes", "dpk_fused",
-           "dpk_set_tail_plan", "dpk_set_tile_waves", "dpk_debug_split", "dpk_debug_resources", "dpk_debug_generic_forms", "dpk_debug_sampler_kernels",
+           "dpk_set_tail_plan", "dpk_set_tile_waves", "dpk_debug_split", "dpk_debug_resources", "dpk_debug_generic_forms", "dpk_debug_grad_forms", "dpk_debug_sampler_kernels",
            "dpk_profile",
            "dpk_profile_read", "dpk_kernel_geometry", "dpk_last_error", "dpk_destroy")
 
@@ -77,6 +77,10 @@ def lib() -> ctypes.CDLL:
     L.dpk_sample_start.argtypes = [vp, vp, vp, vp, vp, i32, u64, vp, i32, vp, i32, vp, vp]
     L.dpk_q_sample.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp, u64, vp]
     L.dpk_diff_loss.argtypes = [vp, vp, vp, vp, i32, vp, u64, vp, vp, vp, i32, vp]
+    L.dpk_diff_loss_grad.argtypes = [vp, vp, vp, vp, i32, vp, u64, ctypes.c_float, vp, vp, i32, vp]
+    L.dpk_param_count.argtypes = [vp]
+    L.dpk_param_layout.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(i64), ctypes.POINTER(i64)]
+    L.dpk_debug_grad_forms.argtypes = [vp, ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint)]
     L.dpk_ddim_update.argtypes = [vp, vp, vp, vp, vp, i64, i32, u64, vp]
     L.dpk_ddim_update_noise.argtypes = [vp, vp, vp, vp, vp, i64, i32, u64, vp, vp]
     L.dpk_debug_split.argtypes = [vp, i32, ctypes.POINTER(i32)]

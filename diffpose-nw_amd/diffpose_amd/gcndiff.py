@@ -111,8 +111,9 @@ class _HipModel:
 
     def train(self, mode: bool = True):
         if mode:
-            raise NotImplementedError(f"{type(self).__name__} is inference-only (training is out of scope, "
-                                      "SURVEY §8f f4)")
+            raise NotImplementedError(f"{type(self).__name__} has no train mode (no dropout on the device): take "
+                                      "gradient steps in eval mode with HipGCNdiff.diffusion_loss_grad or "
+                                      "runner.Diffpose.train_step (SURVEY §8f f4)")
         return self.eval()
 
     def to(self, *a, **k):
@@ -264,6 +265,20 @@ class _HipModel:
         w = ctypes.c_uint(0)
         _lib.check(self._h, "dpk_debug_generic_forms", _lib.lib().dpk_debug_generic_forms(self._h, ctypes.byref(w)))
         return {name for i, name in enumerate(self.GENERIC_FORMS) if (w.value >> i) & 1}
+
+    # bit i of dpk_debug_grad_forms' second word (csrc/dpk_generic_bwd.inc, dpkg::BwdForm)
+    GRAD_FORMS = ("dw_partial<vec>", "dw_partial<scalar>", "attention_bwd<T>", "ln_bwd", "graph_t<T>", "graph_t<F>",
+                  "cheb_t", "dlg<T>", "temb_bwd", "attention_bwd<F>", "dlg<F>")
+
+    def debug_grad_forms(self):
+        """Test hook (dpk_debug_grad_forms): (GENERIC_FORMS names of the training forward's and the dX GEMMs'
+        launches, GRAD_FORMS names of the backward's own kernels) of the ``diffusion_loss_grad`` calls since the
+        last read."""
+        a, b = ctypes.c_uint(0), ctypes.c_uint(0)
+        _lib.check(self._h, "dpk_debug_grad_forms",
+                   _lib.lib().dpk_debug_grad_forms(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return ({n for i, n in enumerate(self.GENERIC_FORMS) if (a.value >> i) & 1},
+                {n for i, n in enumerate(self.GRAD_FORMS) if (b.value >> i) & 1})
 
     def debug_sampler_kernels(self) -> set:
         """Test hook (dpk_debug_sampler_kernels): the names (_lib.sampler_kernel_name, e.g.
@@ -487,6 +502,62 @@ class HipGCNdiff(_HipModel):
                                       eps.data_ptr() if eps is not None else None, n, stream)
         _lib.check(self._h, "dpk_diff_loss", rc)
         return (loss, xt, eps) if return_parts else loss
+
+    def param_layout(self):
+        """dpk_param_layout as a list of (name, offset, numel) in state_dict order, and the flat array's extent in
+        floats (the last entry's offset + numel)."""
+        L = _lib.lib()
+        out = []
+        name, off, num = ctypes.c_char_p(), ctypes.c_int64(), ctypes.c_int64()
+        for i in range(int(L.dpk_param_count(self._h))):
+            _lib.check(self._h, "dpk_param_layout",
+                       L.dpk_param_layout(self._h, i, ctypes.byref(name), ctypes.byref(off), ctypes.byref(num)))
+            out.append((name.value.decode(), int(off.value), int(num.value)))
+        return out, (out[-1][1] + out[-1][2] if out else 0)
+
+    def diffusion_loss_grad(self, x0, t, betas, noise_scale=None, noise=None, seed: int = 0, mask=None, weight=None):
+        """``diffusion_loss`` and its gradient: ``(loss [N], grads)`` with ``grads`` an OrderedDict name -> view of one
+        flat device tensor (``grads.flat``), every parameter of the state_dict under its name and with the reference's
+        shape: d(sum_n weight * loss[n]) / d parameter, what ``loss_diff.backward()`` leaves in ``p.grad``
+        (runners/diffpose_frame.py:226-229) for the default ``weight`` = 1 / N.  Eval mode (dropout off), fp32, the
+        per-op kernels on every handle; the same arguments give bitwise the same gradients.  Arguments and their
+        checks as in ``diffusion_loss``; a rank holding a shard of a batch of B poses passes ``weight=1 / B``."""
+        from collections import OrderedDict
+
+        from .weights import param_shapes
+
+        x0 = self._check_x(x0)
+        b = betas.detach().cpu().numpy() if torch.is_tensor(betas) else np.asarray(betas)
+        b = np.ascontiguousarray(b, dtype=np.float32)
+        if self._sched_key is None or self._sched_key[1] != b.tobytes():
+            self.set_schedule([0], b, 0.0)
+        n = x0.shape[0]
+        tt = self._loss_timesteps(t, n, b.shape[0])
+        _t0, sc, rows, e = self._check_start(x0, 0, noise_scale, noise, names=("noise_scale", "noise"))
+        self._sync_mask(mask)
+        self._check_mask_batch(n)
+        self._note_mask_use()
+        weight = (1.0 / n if n else 0.0) if weight is None else float(weight)
+        layout, total = self.param_layout()
+        loss = torch.empty(n, dtype=torch.float32, device=self.device)
+        flat = torch.zeros(total, dtype=torch.float32, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = _lib.lib().dpk_diff_loss_grad(self._h, x0.data_ptr(), tt.data_ptr(),
+                                           sc.data_ptr() if sc is not None else None, rows,
+                                           e.data_ptr() if e is not None else None,
+                                           ctypes.c_uint64(seed & (2**64 - 1)), ctypes.c_float(weight),
+                                           loss.data_ptr(), flat.data_ptr(), n, stream)
+        _lib.check(self._h, "dpk_diff_loss_grad", rc)
+        shapes = param_shapes(hid=self.hid_dim, n_layers=self.num_layer, n_pts=self.n_pts, coords=self.coords_dim)
+
+        class _Grads(OrderedDict):
+            pass
+
+        grads = _Grads()
+        for name, off, num in layout:
+            grads[name] = flat[off:off + num].view(shapes[name])
+        grads.flat = flat
+        return loss, grads
 
     def ddim_update(self, xt, et, step: int, seed: int = 0, want_x0: bool = True, noise=None):
         """x_{t-1} (and x0) from an external eps for schedule step ``step``; ``noise``: this step's

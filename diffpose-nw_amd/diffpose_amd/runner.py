@@ -8,6 +8,7 @@ Mirrors ``Diffpose`` in ``runners/diffpose_frame.py``:
 | ``create_diffusion_model`` | 118-132 | ``HipGCNdiff`` handle, optional checkpoint |
 | ``create_pose_model`` | 134-154 | ``HipGCNpose`` handle, optional checkpoint |
 | ``test_hyber`` | 270-420 | pose front-end plus uvxyz assembly (one launch); the K-step DDIM sampler (one launch); per-frame MPJPE / P-MPJPE (one launch); the reference's per-action accounting on the host. Returns (p1, p2) in mm |
+| ``train_step`` | 211-233 for one batch | draws, the per-pose losses and every parameter's gradient in one ``dpk_diff_loss_grad`` call (eval mode), ``.grad`` on the caller's torch parameters, clipping, ``optimizer.step()``, the weights loaded back. Returns ``loss_diff`` |
 | ``diffusion_loss`` | 203-233, forward only | the training objective in eval mode: per-pose-t noising, eps and the per-pose sums in one ``dpk_diff_loss`` call per batch; the reference's ``update(loss_diff, n)`` on the host. Returns the epoch average |
 
 Several ranks (``torch.distributed`` initialised with world size > 1, one process per GPU): every
@@ -381,6 +382,43 @@ class Diffpose:
                 epoch.update(float(loss.cpu().mean()), B)                      # :226's batch mean, :233
         self.epoch_loss_diff = epoch.avg
         return epoch.avg
+
+    def train_step(self, targets_uvxyz, noise_scale, optimizer, params, generator=None):
+        """One gradient step on one batch: the body of the reference's training loop (runners/diffpose_frame.py:211-233)
+        with the model in eval mode (dropout off).  Draws ``e`` (:214) and the antithetic ``t`` (:216-218) as
+        ``diffusion_loss`` does (torch's default generator, or ``generator``), takes the per-pose losses and every
+        parameter's gradient in one ``HipGCNdiff.diffusion_loss_grad`` call, assigns them as ``.grad`` of ``params``
+        (the caller's dict name -> torch parameter on the model's device, the state_dict's names), clips with
+        ``config.optim.grad_clip`` when the config has one (:229), calls ``optimizer.step()`` (:230) and loads the
+        updated ``params`` back into the handle.  Returns ``loss_diff`` (a float, :226).
+
+        The reference trains with dropout ``config.model.dropout``; the device has no dropout masks, so a config whose
+        dropout is not 0 raises NotImplementedError unless ``args.train_without_dropout`` is set."""
+        from .schedule import training_timesteps
+
+        p_drop = float(getattr(self.config.model, "dropout", 0.0) or 0.0)
+        if p_drop != 0.0 and not getattr(self.args, "train_without_dropout", False):
+            raise NotImplementedError(f"config.model.dropout = {p_drop}: the device backward runs without dropout masks; "
+                                      "set args.train_without_dropout to train in eval mode, or dropout to 0")
+        x0 = torch.as_tensor(targets_uvxyz).detach().to(torch.float32)
+        noise_scale = torch.as_tensor(noise_scale).detach().to(torch.float32)
+        B = x0.shape[0]
+        if tuple(x0.shape) != (B, self.n_pts, 5) or noise_scale.shape != x0.shape or B == 0:
+            raise ValueError(f"targets_uvxyz and noise_scale must be (B, {self.n_pts}, 5) with B > 0, got "
+                             f"{tuple(x0.shape)} and {tuple(noise_scale.shape)}")
+        e = torch.randn((B, self.n_pts, 5), generator=generator)                   # :214
+        t = training_timesteps(B, self.num_timesteps, generator=generator)        # :216-218
+        dev = lambda a: a.to(self.device)   # noqa: E731
+        loss, grads = self.model_diff.diffusion_loss_grad(dev(x0), t, self.betas, noise_scale=dev(noise_scale),
+                                                          noise=dev(e), mask=self.src_mask)
+        for name, g in grads.items():
+            params[name].grad = g.to(params[name].dtype)
+        clip = getattr(getattr(self.config, "optim", None), "grad_clip", None)
+        if clip is not None:
+            torch.nn.utils.clip_grad_norm_(list(params.values()), clip)
+        optimizer.step()
+        self.model_diff.load_state_dict({k: v.detach() for k, v in params.items()})
+        return float(loss.mean())
 
     def log_performance_metrics(self, output_path=None):
         """Summary of the per-batch inference times and peak-memory deltas collected under

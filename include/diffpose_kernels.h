@@ -226,6 +226,42 @@ int dpk_diff_loss(dpk_handle* h, const float* x0_dev, const float* t_dev, const 
                   const float* noise_dev, uint64_t seed, float* loss_dev, float* xt_dev, float* eps_dev, int N,
                   void* stream);
 
+/* The gradient of that objective with respect to every parameter of GCNdiff, in eval mode (dropout off) and fp32:
+ * what the reference's loss_diff.backward() leaves in p.grad (runners/diffpose_frame.py:219-229) for
+ *   L = sum over n of weight * loss_n
+ * so weight = 1 / N gives the gradient of the reference's loss_diff (:226), and a rank that holds a shard of a batch
+ * of B poses passes 1 / B, so that the shards' gradients add.
+ *   x0_dev, t_dev, scale_dev, scale_rows, noise_dev, seed   exactly dpk_diff_loss's: the noising, the clamped table
+ *             index, the counter-based draws at step -1; the handle's key mask and per-pose masks as in dpk_eps
+ *   loss_dev  [N] or NULL: the per-pose loss of this call's own forward, the per-op fp32 forward (on a handle with a
+ *             persistent sampler instance it is not promised bitwise equal to dpk_diff_loss, which runs the sampler's
+ *             tiles; both stand inside the same bar against the float64 model)
+ *   grads_dev one flat fp32 array, dL/dtheta of every parameter in the state_dict's order, under its names and in
+ *             its torch layouts (nn.Linear [out,in], ChebConv [3,1,in,out], A_hat [n_pts,n_pts]; the fused QKV block
+ *             of the arena split back into self_attn.linears.0/1/2).  dpk_param_count entries, entry i described by
+ *             dpk_param_layout: its name (valid for the process's life), its offset in floats (a multiple of 4) and its
+ *             numel.  The array's extent is the last entry's offset + numel floats; every float of it is written (zero
+ *             where a gradient is zero, and in the padding between entries).
+ * The gradient of A_hat goes back through the GraphNet Laplacian c_i^-1/2 A_ij c_j^-1/2, c = column sums + 1e-5
+ * (models/GraFormer.py:174-178; both uses of a layer); the ChebConvs' adjacency is a constant; the timestep MLP is
+ * differentiated down to temb.dense.0, per pose.  No gradient with respect to the input.
+ * Every handle runs it on the per-op kernels (csrc/dpk_generic_bwd.inc): a training forward that keeps what the
+ * backward reads in the call's scratch (DESIGN.md section 3.4 has the floats per pose), dA = dC W^T on the forward's GEMM
+ * kernels against a transposed copy of the weights, dW = A^T dC and every other sum over rows or poses as a store pass
+ * of partials over a fixed row partition plus an ordered sum pass (no float atomics): two calls with the same
+ * arguments on the same handle give bitwise the same grads_dev.  A handle with a persistent sampler instance builds
+ * its per-op model and the transposed weights on the first call (and again after new weights or a new graph), which
+ * waits for the device; its sampling path is untouched (dpk_fused stays 1).
+ * DPK_E_UNSUPPORTED on a GCNpose handle and when the handle's gemm mode is not 0 (the backward is fp32);
+ * DPK_E_STATE when `stream` is capturing (the call allocates); otherwise dpk_diff_loss's refusals and the caller-memory
+ * contract above (N = 0 touches nothing). */
+int dpk_diff_loss_grad(dpk_handle* h, const float* x0_dev, const float* t_dev, const float* scale_dev, int scale_rows,
+                       const float* noise_dev, uint64_t seed, float weight, float* loss_dev, float* grads_dev, int N,
+                       void* stream);
+/* Parameters of a GCNdiff handle (0 for NULL or a GCNpose handle), and entry i of their layout in grads_dev. */
+int dpk_param_count(const dpk_handle* h);
+int dpk_param_layout(const dpk_handle* h, int i, const char** name, int64_t* offset, int64_t* numel);
+
 /* One DDIM update for an externally computed eps (generic model callables):
  * the per-element body of common/utils_diff.py:59-65 for schedule step `step`
  * (0 = first executed step, t = seq[K-1]).  x0_dev may be NULL; xnext_dev may be xt_dev. */
@@ -411,6 +447,12 @@ int dpk_profile_read(dpk_handle* h, float* ms_out, int cap, int* count);
 int dpk_debug_split(dpk_handle* h, int mode, int* fallbacks);
 int dpk_debug_resources(dpk_handle* h, int* out, int n);
 int dpk_debug_generic_forms(dpk_handle* h, unsigned* forms);
+/* dpk_debug_grad_forms: the same for dpk_diff_loss_grad, then cleared: *gemm_forms the dpk_debug_generic_forms bits of
+ * its training forward and of its dX GEMMs, *bwd_forms the backward's own (bit 0 dw_partial with 16-byte loads, 1 with
+ * scalar loads, 2 attention_bwd with the pose's rows staged in LDS, 3 ln_bwd, 4..5 graph on L_g^T staged / unstaged,
+ * 6 cheb_t, 7 dlg_partial staged (+ dlg_chain), 8 the timestep MLP's backward, 9 attention_bwd unstaged, 10 dlg_partial
+ * unstaged). */
+int dpk_debug_grad_forms(dpk_handle* h, unsigned* gemm_forms, unsigned* bwd_forms);
 int dpk_debug_sampler_kernels(dpk_handle* h, uint32_t* ids, int cap, int* count);
 
 /* Poses per workgroup of the sampler kernel and its static LDS bytes (for docs/bench). */
