@@ -24,39 +24,17 @@ namespace dpkg {
 constexpr int GJ_MAX = 32;
 enum { G_BIAS = 0, G_RELU = 1, G_RESID = 2, G_RESID_RELU = 3, G_RELU_TEMB = 4 };
 
-// The kernel forms gen_forward chooses between per call (from the shape, the batch and pointer alignment),
-// one bit each: GenModel::forms collects the bits of what was launched, dpk_debug_generic_forms reads and
-// clears them (test hook; diffpose_amd/gcndiff.py GENERIC_FORMS names the bits in this order).
-enum GenForm : unsigned {
-    F_GEMM_NARROW = 1u << 0,
-    F_GEMM_SK4 = 1u << 1,
-    F_GEMM_SK2 = 1u << 2,
-    F_GEMM_128_VEC = 1u << 3,
-    F_GEMM_128_SCALAR = 1u << 4,
-    F_GEMM_64_VEC = 1u << 5,
-    F_GEMM_64_SCALAR = 1u << 6,
-    F_GEMM_32_VEC = 1u << 7,
-    F_GEMM_32_SCALAR = 1u << 8,
-    F_ATTENTION_TT = 1u << 9,     // attention<STAGE, VEC>
-    F_ATTENTION_TF = 1u << 10,
-    F_ATTENTION_FF = 1u << 11,
-    F_GRAPH_T = 1u << 12,         // graph<STAGE>
-    F_GRAPH_F = 1u << 13,
-    F_CHEB_T = 1u << 14,          // cheb_basis<STAGE>
-    F_CHEB_F = 1u << 15,
-};
-
 // C[M][N] (row stride ldc) = epilogue(A[M][K] (lda) x W[K][N] + bias) on the fp32 matrix cores:
 // v_mfma_f32_16x16x4_f32 (exact fp32 products, fp32 accumulation).  A BM x 64 output tile per
 // workgroup of 4 waves, each wave 32 x 64 (BM 128), 32 x 32 (BM 64) or 16 x 32 (BM 32) = NI x NJ MFMA tiles
-// (gen_forward picks BM per shape so the tiles spread evenly over the CUs); A and W staged through LDS in
+// (gemm_choice picks BM per shape so the tiles spread evenly over the CUs); A and W staged through LDS in
 // k-blocks of 32 (row strides 36 and 80 floats: the fragment reads below hit 64 distinct banks), the
 // next k-block's global loads issued before the current block's MFMAs (register double buffer).
 // VEC: 16-byte loads and LDS stores (K, N, lda multiples of 4 and 16-byte aligned A / W).  MFMA
 // operand layout: lane l feeds row/column (l & 15) at k = (l >> 4) of each 4-k step; the accumulator
 // holds rows 4 (l >> 4) + r, column (l & 15).
 // G_RELU_TEMB adds tp[(row / rpp) * tp_stride + col] after the relu (tp_stride 0: one row for all).
-constexpr int GBN = 64, GKB = 32, GA_LD = 36, GW_LD = 80;
+constexpr int GKB = 32, GA_LD = 36, GW_LD = 80;   // GBN = 64 columns: dpk_genplan.inc
 template <int BM, bool VEC>
 __global__ void __launch_bounds__(256) gemm(const float* __restrict__ A, int lda, const float* __restrict__ W,
                                             const float* __restrict__ bias, float* C, int ldc, int M, int N, int K,
@@ -158,11 +136,10 @@ __global__ void __launch_bounds__(256) gemm(const float* __restrict__ A, int lda
 // every thread finishes float4s of the tile (one 16-byte store each).  Many short k-loops in flight instead of
 // a few long ones: these GEMMs are latency-bound (M = 17 x poses rows, K, N of a few hundred),
 // 10-20 % faster than gemm<BM> at the hid-128 shapes (profiles/r04_gen_gemm_probe.txt).
-// Wp: the weights packed by gen_pack, [KC = ceil(K/16)][NTp][64 lanes][4]: lane l, element s of chunk c and
+// Wp: the weights packed by pack_fill, [KC = ceil(K/16)][NTp][64 lanes][4]: lane l, element s of chunk c and
 // column tile t = W[16c + 4 (l >> 4) + s][16t + (l & 15)] (zero outside K x N; NTp = column tiles rounded
 // up to NJ).  Needs K, N, lda, ldc multiples of 4, 16-byte aligned A, C, bias, tp, and M * lda * 4 + K * 4
-// below 2^31 (the range-check sentinel).
-constexpr unsigned SK_OOR = 0x80000000u;
+// below 2^31 (the range-check sentinel SK_OOR).
 template <int NJ>
 __global__ void __launch_bounds__(256) gemm_sk(const float* __restrict__ A, int lda, const float* __restrict__ Wp,
                                                const float* __restrict__ bias, float* C, int ldc, int M, int N, int K,
@@ -550,12 +527,18 @@ __global__ void __launch_bounds__(256) cheb_basis(const float* __restrict__ T1, 
 }
 
 // temb_proj_l(swish(dense1(swish(dense0(emb(t)))))) for every layer l (gcndiff.py:15-33, :46):
-// one workgroup per t value; W0 [D][E], W1 [E][E], WP [L][E][D] (k-major), dynamic LDS D + 2E floats
+// one workgroup per t value; W0 [D][E], W1 [E][E], WP [L][E][D] (k-major), dynamic LDS D + 2E floats.
+// STASH (the training forward): what the MLP's backward reads is kept per t value, emb [D], the pre-activations
+// u0, u1 and the activations h0, h1 [E]; tproj is bitwise temb<false>'s.
+struct TembStash {
+    float *emb, *u0, *h0, *u1, *h1;
+};
+template <bool STASH>
 __global__ void __launch_bounds__(256) temb(const float* __restrict__ W0, const float* __restrict__ B0,
                                             const float* __restrict__ W1, const float* __restrict__ B1,
                                             const float* __restrict__ WP, const float* __restrict__ BP,
                                             const float* __restrict__ tvals, int tstride, int D, int E, int L,
-                                            float neg_scale, float* __restrict__ tproj) {
+                                            float neg_scale, float* __restrict__ tproj, TembStash keep) {
     extern __shared__ float tsm[];
     float* emb = tsm;
     float* h0 = tsm + D;
@@ -570,6 +553,7 @@ __global__ void __launch_bounds__(256) temb(const float* __restrict__ W0, const 
         } else {
             emb[i] = 0.f;   // odd hid_dim: F.pad (gcndiff.py:31-32)
         }
+        if constexpr (STASH) keep.emb[(size_t)blockIdx.x * D + i] = emb[i];
     }
     __syncthreads();
     for (int o = threadIdx.x; o < E; o += 256) {
@@ -577,6 +561,7 @@ __global__ void __launch_bounds__(256) temb(const float* __restrict__ W0, const 
         for (int k = 0; k < D; ++k) acc = fmaf(emb[k], W0[(size_t)k * E + o], acc);
         const float v = acc + B0[o];
         h0[o] = v * (1.0f / (1.0f + expf(-v)));
+        if constexpr (STASH) keep.u0[(size_t)blockIdx.x * E + o] = v, keep.h0[(size_t)blockIdx.x * E + o] = h0[o];
     }
     __syncthreads();
     for (int o = threadIdx.x; o < E; o += 256) {
@@ -584,6 +569,7 @@ __global__ void __launch_bounds__(256) temb(const float* __restrict__ W0, const 
         for (int k = 0; k < E; ++k) acc = fmaf(h0[k], W1[(size_t)k * E + o], acc);
         const float v = acc + B1[o];
         h1[o] = v * (1.0f / (1.0f + expf(-v)));
+        if constexpr (STASH) keep.u1[(size_t)blockIdx.x * E + o] = v, keep.h1[(size_t)blockIdx.x * E + o] = h1[o];
     }
     __syncthreads();
     for (int o = threadIdx.x; o < L * D; o += 256) {
@@ -712,18 +698,41 @@ struct GenGraph {
     hipGraphExec_t exec = nullptr;
     uint64_t last_use = 0;
 };
-// A GEMM weight block [K][N] of the arena (offset w) repacked into gemm_sk's fragment order at offset off
-// of the packed arena
-struct GenPack {
-    size_t w, off;
-    int K, N, NJ;
-};
-struct GenModel {
-    const Stage& s;            // the handle's host staging of the weights and the graph; `dev` is its device copy
+// A weight arena on the device with the gemm_sk copies of its GEMM blocks (dpk_genplan.inc: pack_plan, pack_fill):
+// the forward's over the staging, the backward's over the transposed arena.  Grow-only: a new upload of the same
+// shape reuses the allocations.
+struct GemmArena {
+    float* dev = nullptr;      // device arena
+    float* devp = nullptr;     // device packed arena
+    size_t dev_floats = 0, devp_floats = 0;   // allocated
     std::vector<GenPack> packs;
     std::vector<float> hp;     // host staging of the packed arena
-    float* devp = nullptr;     // device packed arena
-    float* dev = nullptr;      // device arena
+    static int put(dpk_handle* h, float*& d, size_t& cap, const float* src, size_t n) {
+        if (cap < n) {
+            if (d) HIPCHK(h, hipFree(d));
+            d = nullptr, cap = 0;
+            HIPCHK(h, hipMalloc(&d, n * 4));
+            cap = n;
+        }
+        if (n) HIPCHK(h, hipMemcpy(d, src, n * 4, hipMemcpyHostToDevice));
+        return DPK_OK;
+    }
+    // the caller has drained the device: launches in flight may read the arena
+    int upload(dpk_handle* h, const float* host, size_t floats, const std::vector<PackBlock>& blocks) {
+        const size_t pf = pack_plan(blocks, packs);
+        pack_fill(packs, host, pf, hp);
+        const int rc = put(h, dev, dev_floats, host, floats);
+        return rc ? rc : put(h, devp, devp_floats, hp.data(), hp.size());
+    }
+    void free() {
+        if (dev) (void)hipFree(dev);
+        if (devp) (void)hipFree(devp);
+        dev = devp = nullptr, dev_floats = devp_floats = 0;
+    }
+};
+struct GenModel {
+    const Stage& s;            // the handle's host staging of the weights and the graph; arena.dev is its device copy
+    GemmArena arena;
     std::vector<GenGraph> graphs;   // recorded K-step loops (at most GEN_GRAPHS, least recently used out)
     uint64_t use_clock = 0;
     unsigned forms = 0;        // dpkg::GenForm bits of the kernel forms launched (or recorded) since the last read
@@ -758,52 +767,14 @@ static void gen_free(GenModel* g) {
     if (!g) return;
     (void)hipDeviceSynchronize();
     gen_drop_graphs(g, nullptr);
-    if (g->dev) (void)hipFree(g->dev);
-    if (g->devp) (void)hipFree(g->devp);
+    g->arena.free();
     delete g;
-}
-
-// gemm_sk's copies of the hidden-width GEMM weights (and the input ChebConv's when K % 4 == 0): NJ = 4
-// column tiles per workgroup where the column tiles divide by 4 (N = 128, 256, 384, ...), else 2
-static void gen_pack(GenModel* g) {
-    g->packs.clear();
-    size_t off = 0;
-    auto add = [&](size_t w, int K, int N) {
-        if (K % 4 || N % 4 || N <= 8) return;
-        const int NT16 = (N + 15) / 16, NJ = NT16 % 4 == 0 ? 4 : 2, NTp = (NT16 + NJ - 1) / NJ * NJ;
-        g->packs.push_back(GenPack{w, off, K, N, NJ});
-        off += (size_t)((K + 15) / 16) * NTp * 256;
-    };
-    const int D = g->s.D;
-    for (const GenLayer& o : g->s.lay) {
-        add(o.wqkv, D, 3 * D), add(o.wo, D, D), add(o.w1, D, 2 * D), add(o.w2, 2 * D, D);
-        add(o.wc1, 3 * D, D), add(o.wc2, 3 * D, D);
-    }
-    add(g->s.win, 3 * g->s.cin, D);
-    g->hp.assign(off, 0.f);
-    for (const GenPack& p : g->packs) {
-        const int KC = (p.K + 15) / 16, NT16 = (p.N + 15) / 16, NTp = (NT16 + p.NJ - 1) / p.NJ * p.NJ;
-        const float* W = g->s.h.data() + p.w;
-        float* dst = g->hp.data() + p.off;
-        for (int c = 0; c < KC; ++c)
-            for (int t = 0; t < NT16; ++t)
-                for (int l = 0; l < 64; ++l)
-                    for (int s = 0; s < 4; ++s) {
-                        const int k = 16 * c + 4 * (l >> 4) + s, n = 16 * t + (l & 15);
-                        if (k < p.K && n < p.N) dst[(((size_t)c * NTp + t) * 64 + l) * 4 + s] = W[(size_t)k * p.N + n];
-                    }
-    }
 }
 
 static int gen_upload(dpk_handle* h, GenModel* g) {
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipDeviceSynchronize());   // launches in flight may read the arena
-    if (!g->dev) HIPCHK(h, hipMalloc(&g->dev, g->s.floats * 4));
-    HIPCHK(h, hipMemcpy(g->dev, g->s.h.data(), g->s.floats * 4, hipMemcpyHostToDevice));
-    gen_pack(g);
-    if (!g->devp && !g->hp.empty()) HIPCHK(h, hipMalloc(&g->devp, g->hp.size() * 4));
-    if (!g->hp.empty()) HIPCHK(h, hipMemcpy(g->devp, g->hp.data(), g->hp.size() * 4, hipMemcpyHostToDevice));
-    return DPK_OK;
+    return g->arena.upload(h, g->s.h.data(), g->s.floats, gen_pack_blocks(g->s));
 }
 
 // n floats of scratch for a call off the shipped shape (call_scratch; per-op handles, and the timestep
@@ -824,152 +795,122 @@ static int gen_scratch(dpk_handle* h, hipStream_t st, bool cap, size_t n, float*
     return rc;
 }
 
-static inline unsigned gen_blocks(long long n) { return (unsigned)((n + 255) / 256); }
+// The ops of one call over N poses, as launches on st: each asks dpk_genplan.inc which form runs, at which grid and
+// LDS size, notes the form's bit in `forms` and launches it.  Built once per call (the A/B switches DPK_GEN_GEMM and
+// DPK_GEN_BM are read here, so they hold for every GEMM of the call, the backward's included); the inference
+// forward, the training forward and the backward's dX GEMMs all go through it.
+struct GenOps {
+    const Stage& s;
+    const float* W;            // the forward's device arena
+    hipStream_t st;
+    int N, n_cu;
+    unsigned mask;
+    const unsigned* pmask;
+    unsigned& forms;           // dpkg::GenForm bits
+    GenSwitches sw;
+    GenOps(const GenModel* g, hipStream_t st_, int N_, unsigned mask_, const unsigned* pmask_, int n_cu_, unsigned& forms_)
+        : s(g->s), W(g->arena.dev), st(st_), N(N_), n_cu(n_cu_), mask(mask_), pmask(pmask_), forms(forms_),
+          sw(gen_switches(getenv("DPK_GEN_GEMM"), getenv("DPK_GEN_BM"))) {}
+    int M() const { return N * s.J; }
 
-// floats of activation scratch for N poses (gen_forward's buffers)
-static size_t gen_act_floats(const GenModel* g, int N) {
-    const size_t M = (size_t)N * g->s.J, D = g->s.D;
-    // Zs holds a Chebyshev operand [X | T1X | T2X] of the hidden width or of the input (3 * cin)
-    const size_t Z = 3 * std::max(D, (size_t)g->s.cin);
-    return M * (D + D + Z + D + 2 * D + 2 * D) + M * (size_t)std::max(g->s.cout, 4);
-}
+    // c [rows][Nn] (row stride ldc) = epilogue(a [rows][K] x the block at offset w of `ar` + bias); tpl, tps:
+    // G_RELU_TEMB's rows.  packed false: the block has no gemm_sk copy of its own (the timestep MLP's stacked
+    // projections [L D][E], whose L parts have)
+    void gemm(const GemmArena& ar, const float* a, int rows, int K, size_t w, const float* bias, float* c, int ldc, int Nn,
+              int mode, const float* tpl = nullptr, int tps = 0, bool packed = true) const {
+        const float* Wb = ar.dev + w;
+        const GenPack* pk = packed ? find_pack(ar.packs, w, K, Nn) : nullptr;
+        const auto at = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+        const GemmChoice g =
+            gemm_choice(rows, K, Nn, ldc, at(a), at(Wb), at(bias), at(c), at(tpl), tps, pk ? pk->NJ : 0, n_cu, sw);
+        forms |= g.form;
+        const dim3 grid(g.gx, g.gy);
+#define DPKG_GEMM(KERNEL_, W_) \
+    hipLaunchKernelGGL(KERNEL_, grid, dim3(256), g.lds, st, a, K, W_, bias, c, ldc, rows, Nn, K, mode, tpl, tps, s.J)
+        if (g.kind == GEMM_NARROW) DPKG_GEMM(dpkg::gemm_narrow, Wb);
+        else if (g.kind == GEMM_SK4) DPKG_GEMM(dpkg::gemm_sk<4>, ar.devp + pk->off);
+        else if (g.kind == GEMM_SK2) DPKG_GEMM(dpkg::gemm_sk<2>, ar.devp + pk->off);
+        else if (g.bm == 128 && g.vec) DPKG_GEMM((dpkg::gemm<128, true>), Wb);
+        else if (g.bm == 128) DPKG_GEMM((dpkg::gemm<128, false>), Wb);
+        else if (g.bm == 64 && g.vec) DPKG_GEMM((dpkg::gemm<64, true>), Wb);
+        else if (g.bm == 64) DPKG_GEMM((dpkg::gemm<64, false>), Wb);
+        else if (g.vec) DPKG_GEMM((dpkg::gemm<32, true>), Wb);
+        else DPKG_GEMM((dpkg::gemm<32, false>), Wb);
+#undef DPKG_GEMM
+    }
+    // Z = [X | T1 X | T2 X] of xin [N][J][C]
+    void cheb(const float* xin, int C, float* Z) const {
+        const StageChoice c = cheb_choice(N, s.J, C);
+        forms |= c.stage ? dpkg::F_CHEB_T : dpkg::F_CHEB_F;
+        auto* kernel = c.stage ? dpkg::cheb_basis<true> : dpkg::cheb_basis<false>;
+        hipLaunchKernelGGL(kernel, dim3(c.blocks), dim3(256), c.lds, st, W + s.t1, W + s.t2, xin, Z, N, s.J, C);
+    }
+    // y = Lm xin with Lm a layer's Laplacian, or (bwd given: the backward, its form noted there) its transpose
+    void graph(const float* Lm, const float* xin, int C, float* y, unsigned* bwd = nullptr) const {
+        const StageChoice c = graph_choice(N, s.J, C);
+        if (bwd) *bwd |= c.stage ? dpkg::B_GRAPH_T_STAGED : dpkg::B_GRAPH_T_GLOBAL;
+        else forms |= c.stage ? dpkg::F_GRAPH_T : dpkg::F_GRAPH_F;
+        auto* kernel = c.stage ? dpkg::graph<true> : dpkg::graph<false>;
+        hipLaunchKernelGGL(kernel, dim3(c.blocks), dim3(256), c.lds, st, Lm, xin, C, y, C, N, s.J, C);
+    }
+    // (the vector form stores 16 bytes at a time to out: see graph on when gen_forward's As is not 16-byte aligned)
+    void attention(const float* qkv, float* out) const {
+        const AttnChoice a = attention_choice(N, s.J, s.D, s.H, reinterpret_cast<uintptr_t>(out));
+        forms |= a.form;
+        auto* kernel = !a.stage ? dpkg::attention<false, false> : a.vec ? dpkg::attention<true, true> : dpkg::attention<true, false>;
+        hipLaunchKernelGGL(kernel, dim3(a.blocks), dim3(256), a.lds, st, qkv, out, N, s.J, s.D, s.H, mask, pmask, a.ppb);
+    }
+    void layer_norm(const float* x, float* y, size_t ga, size_t gb) const {
+        hipLaunchKernelGGL(dpkg::layer_norm, dim3((unsigned)((M() + 3) / 4)), dim3(256), 0, st, x, y, M(), s.D, W + ga, W + gb);
+    }
+    // timestep projections of `count` t values (stride tstride) into tproj [count][L][D]; keep: the training
+    // forward's stash of the MLP's intermediates
+    void temb(const float* tvals, int tstride, int count, float* tproj, const dpkg::TembStash* keep = nullptr) const {
+        const float neg = -(float)(log(10000.0) / (double)(s.D / 2 - 1));
+        const size_t lds = (size_t)(s.D + 2 * s.E) * 4;
+        hipLaunchKernelGGL(keep ? dpkg::temb<true> : dpkg::temb<false>, dim3((unsigned)count), dim3(256), lds, st, W + s.d0w,
+                           W + s.d0b, W + s.d1w, W + s.d1b, W + s.wtp, W + s.btp, tvals, tstride, s.D, s.E, s.L, neg, tproj,
+                           keep ? *keep : dpkg::TembStash{});
+    }
+};
 
-// One GCNdiff / GCNpose forward of N poses x (N, J, cin) -> y (N, J, cout).  tp: per-layer timestep
+// One GCNdiff / GCNpose forward of op.N poses x (N, J, cin) -> y (N, J, cout).  tp: per-layer timestep
 // projections, rows of L*D floats (tp_stride 0: one row for every pose, else L*D per pose); null for
-// GCNpose.  S: gen_act_floats(N) floats of scratch.
-static void gen_forward(GenModel* g, hipStream_t st, const float* x, int N, const float* tp, int tp_stride,
-                        unsigned mask, const unsigned* pmask, float* y, float* S, int n_cu) {
-    const int D = g->s.D, J = g->s.J, M = N * J;
-    const float* W = g->dev;
+// GCNpose.  S: gen_act_floats(N) floats of scratch.  Six buffers reused layer after layer, relu + temb and
+// resid + relu fused into GEMM epilogues.
+static void gen_forward(const GenModel* g, const GenOps& op, const float* x, const float* tp, int tp_stride, float* y,
+                        float* S) {
+    const Stage& s = g->s;
+    const GemmArena& ar = g->arena;
+    const int D = s.D, M = op.M();
+    const float* W = ar.dev;
     float* Hs = S;
     float* Ys = Hs + (size_t)M * D;
     float* Zs = Ys + (size_t)M * D;
-    float* As = Zs + (size_t)M * 3 * std::max(D, g->s.cin);
+    float* As = Zs + (size_t)M * 3 * std::max(D, s.cin);
     float* Fs = As + (size_t)M * D;
     float* Gs = Fs + (size_t)M * 2 * D;
-    // DPK_GEN_GEMM=lds: the LDS-staged gemm<BM> everywhere (A/B)
-    const char* ge = getenv("DPK_GEN_GEMM");
-    const bool sk = !(ge && strcmp(ge, "lds") == 0);
-    auto gemm = [&](const float* a, int K, size_t w, size_t b, float* c, int ldc, int Nn, int mode,
-                    const float* tpl = nullptr, int tps = 0) {
-        // the row-tile height whose tiles finish soonest when dealt out to the CUs (a tile's time taken as
-        // proportional to its height): ceil(tiles / CUs) x BM; the taller tile wins ties
-        const long long nt = (Nn + dpkg::GBN - 1) / dpkg::GBN, cu = std::max(n_cu, 1);
-        int bm = 128;
-        long long best = -1;
-        for (int cand : {128, 64, 32}) {
-            const long long cost = ((M + cand - 1) / cand * nt + cu - 1) / cu * cand;
-            if (best < 0 || cost < best) best = cost, bm = cand;
-        }
-        if (const char* e = getenv("DPK_GEN_BM")) bm = atoi(e) == 128 ? 128 : atoi(e) == 64 ? 64 : atoi(e) == 32 ? 32 : bm;
-        const dim3 grid((unsigned)((M + bm - 1) / bm), (unsigned)nt);
-        // 16-byte operand loads when every row start is 16-byte aligned (the arena's blocks are, by take())
-        auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-        const bool vec = K % 4 == 0 && Nn % 4 == 0 && al16(a) && al16(W + w);
-        if (Nn <= 8 && (size_t)K * Nn * 4 <= 65536) {
-            g->forms |= dpkg::F_GEMM_NARROW;
-            hipLaunchKernelGGL(dpkg::gemm_narrow, dim3((unsigned)((M + 3) / 4)), dim3(256), (size_t)K * Nn * 4, st, a, K,
-                               W + w, W + b, c, ldc, M, Nn, K, mode, tpl, tps, J);
-            return;
-        }
-        const GenPack* pk = nullptr;
-        for (const GenPack& p : g->packs)
-            if (p.w == w && p.K == K && p.N == Nn) pk = &p;
-        if (pk && vec && sk && ldc % 4 == 0 && al16(c) && al16(W + b) && (!tpl || (al16(tpl) && tps % 4 == 0)) &&
-            (size_t)M * K * 4 + (size_t)K * 4 < dpkg::SK_OOR) {
-            const dim3 gs((unsigned)((M + 15) / 16), (unsigned)(((Nn + 15) / 16 + pk->NJ - 1) / pk->NJ));
-            g->forms |= pk->NJ == 4 ? dpkg::F_GEMM_SK4 : dpkg::F_GEMM_SK2;
-            if (pk->NJ == 4)
-                hipLaunchKernelGGL(dpkg::gemm_sk<4>, gs, dim3(256), 0, st, a, K, g->devp + pk->off, W + b, c, ldc, M, Nn,
-                                   K, mode, tpl, tps, J);
-            else
-                hipLaunchKernelGGL(dpkg::gemm_sk<2>, gs, dim3(256), 0, st, a, K, g->devp + pk->off, W + b, c, ldc, M, Nn,
-                                   K, mode, tpl, tps, J);
-            return;
-        }
-#define DPKG_GEMM(BM_, V_) hipLaunchKernelGGL((dpkg::gemm<BM_, V_>), grid, dim3(256), 0, st, a, K, W + w, W + b, c, ldc, M, Nn, K, mode, tpl, tps, J)
-        if (bm == 128) {
-            g->forms |= vec ? dpkg::F_GEMM_128_VEC : dpkg::F_GEMM_128_SCALAR;
-            if (vec) DPKG_GEMM(128, true);
-            else DPKG_GEMM(128, false);
-        } else if (bm == 64) {
-            g->forms |= vec ? dpkg::F_GEMM_64_VEC : dpkg::F_GEMM_64_SCALAR;
-            if (vec) DPKG_GEMM(64, true);
-            else DPKG_GEMM(64, false);
-        } else {
-            g->forms |= vec ? dpkg::F_GEMM_32_VEC : dpkg::F_GEMM_32_SCALAR;
-            if (vec) DPKG_GEMM(32, true);
-            else DPKG_GEMM(32, false);
-        }
-#undef DPKG_GEMM
-    };
-    auto cheb = [&](const float* xin, int C) {
-        const size_t lds = ((size_t)J * C + 2 * J * J) * 4;
-        g->forms |= lds <= 65536 ? dpkg::F_CHEB_T : dpkg::F_CHEB_F;
-        if (lds <= 65536)
-            hipLaunchKernelGGL(dpkg::cheb_basis<true>, dim3((unsigned)N), dim3(256), lds, st, W + g->s.t1, W + g->s.t2, xin,
-                               Zs, N, J, C);
-        else
-            hipLaunchKernelGGL(dpkg::cheb_basis<false>, dim3(gen_blocks((long long)M * C)), dim3(256), 0, st, W + g->s.t1,
-                               W + g->s.t2, xin, Zs, N, J, C);
-    };
-    auto graph = [&](size_t lg, const float* xin, int C, float* yout) {
-        const size_t lds = ((size_t)J * C + J * J) * 4;
-        g->forms |= lds <= 65536 ? dpkg::F_GRAPH_T : dpkg::F_GRAPH_F;
-        if (lds <= 65536)
-            hipLaunchKernelGGL(dpkg::graph<true>, dim3((unsigned)N), dim3(256), lds, st, W + lg, xin, C, yout, C, N, J, C);
-        else
-            hipLaunchKernelGGL(dpkg::graph<false>, dim3(gen_blocks((long long)M * C)), dim3(256), 0, st, W + lg, xin, C,
-                               yout, C, N, J, C);
-    };
-    cheb(x, g->s.cin);
-    gemm(Zs, 3 * g->s.cin, g->s.win, g->s.bin, Hs, D, D, dpkg::G_BIAS);
-    for (int l = 0; l < g->s.L; ++l) {
-        const GenLayer& o = g->s.lay[l];
-        hipLaunchKernelGGL(dpkg::layer_norm, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, Hs, Ys, M, D, W + o.n0a,
-                           W + o.n0b);
-        gemm(Ys, D, o.wqkv, o.bqkv, Zs, 3 * D, 3 * D, dpkg::G_BIAS);
-        // poses per workgroup: enough (head, query) threads to fill 256, within 64 KB of LDS
-        // (the vector form stores 16 bytes at a time to As: see graph on when As is not 16-byte aligned)
-        const bool avec = (D / g->s.H) % 4 == 0 && D % 8 == 0 && (reinterpret_cast<uintptr_t>(As) & 15) == 0;
-        const size_t pose_bytes = (size_t)J * (3 * D + (avec ? 4 : 1)) * 4;
-        const int ppb = std::max(1, std::min(256 / (g->s.H * J), (int)(65536 / pose_bytes)));
-        const unsigned ab = (unsigned)((N + ppb - 1) / ppb);
-        g->forms |= pose_bytes > 65536 ? dpkg::F_ATTENTION_FF : avec ? dpkg::F_ATTENTION_TT : dpkg::F_ATTENTION_TF;
-        if (pose_bytes > 65536)
-            hipLaunchKernelGGL((dpkg::attention<false, false>), dim3((unsigned)N), dim3(256), 0, st, Zs, As, N, J, D,
-                               g->s.H, mask, pmask, 1);
-        else if (avec)
-            hipLaunchKernelGGL((dpkg::attention<true, true>), dim3(ab), dim3(256), pose_bytes * ppb, st, Zs, As, N, J, D,
-                               g->s.H, mask, pmask, ppb);
-        else
-            hipLaunchKernelGGL((dpkg::attention<true, false>), dim3(ab), dim3(256), pose_bytes * ppb, st, Zs, As, N, J,
-                               D, g->s.H, mask, pmask, ppb);
-        gemm(As, D, o.wo, o.bo, Hs, D, D, dpkg::G_RESID);
-        hipLaunchKernelGGL(dpkg::layer_norm, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, Hs, Ys, M, D, W + o.n1a,
-                           W + o.n1b);
-        graph(o.lg, Ys, D, As);
-        gemm(As, D, o.w1, o.b1, Fs, 2 * D, 2 * D, dpkg::G_RELU);
-        graph(o.lg, Fs, 2 * D, Gs);
-        gemm(Gs, 2 * D, o.w2, o.b2, Hs, D, D, dpkg::G_RESID);
-        cheb(Hs, D);
-        if (tp) gemm(Zs, 3 * D, o.wc1, o.bc1, As, D, D, dpkg::G_RELU_TEMB, tp + (size_t)l * D, tp_stride);
-        else gemm(Zs, 3 * D, o.wc1, o.bc1, As, D, D, dpkg::G_RELU);
-        cheb(As, D);
-        gemm(Zs, 3 * D, o.wc2, o.bc2, Hs, D, D, dpkg::G_RESID_RELU);
+    op.cheb(x, s.cin, Zs);
+    op.gemm(ar, Zs, M, 3 * s.cin, s.win, W + s.bin, Hs, D, D, dpkg::G_BIAS);
+    for (int l = 0; l < s.L; ++l) {
+        const GenLayer& o = s.lay[l];
+        op.layer_norm(Hs, Ys, o.n0a, o.n0b);
+        op.gemm(ar, Ys, M, D, o.wqkv, W + o.bqkv, Zs, 3 * D, 3 * D, dpkg::G_BIAS);
+        op.attention(Zs, As);
+        op.gemm(ar, As, M, D, o.wo, W + o.bo, Hs, D, D, dpkg::G_RESID);
+        op.layer_norm(Hs, Ys, o.n1a, o.n1b);
+        op.graph(W + o.lg, Ys, D, As);
+        op.gemm(ar, As, M, D, o.w1, W + o.b1, Fs, 2 * D, 2 * D, dpkg::G_RELU);
+        op.graph(W + o.lg, Fs, 2 * D, Gs);
+        op.gemm(ar, Gs, M, 2 * D, o.w2, W + o.b2, Hs, D, D, dpkg::G_RESID);
+        op.cheb(Hs, D, Zs);
+        op.gemm(ar, Zs, M, 3 * D, o.wc1, W + o.bc1, As, D, D, tp ? dpkg::G_RELU_TEMB : dpkg::G_RELU,
+                tp ? tp + (size_t)l * D : nullptr, tp_stride);
+        op.cheb(As, D, Zs);
+        op.gemm(ar, Zs, M, 3 * D, o.wc2, W + o.bc2, Hs, D, D, dpkg::G_RESID_RELU);
     }
-    cheb(Hs, D);
-    gemm(Zs, 3 * D, g->s.wout, g->s.bout, y, g->s.cout, g->s.cout, dpkg::G_BIAS);
-}
-
-// timestep projections of `count` t values (stride tstride) into tproj [count][L][D]
-static void gen_temb(GenModel* g, hipStream_t st, const float* tvals, int tstride, int count, float* tproj) {
-    const float* W = g->dev;
-    const int half = g->s.D / 2;
-    const float neg = -(float)(log(10000.0) / (double)(half - 1));
-    const size_t lds = (size_t)(g->s.D + 2 * g->s.E) * 4;
-    hipLaunchKernelGGL(dpkg::temb, dim3((unsigned)count), dim3(256), lds, st, W + g->s.d0w, W + g->s.d0b, W + g->s.d1w,
-                       W + g->s.d1b, W + g->s.wtp, W + g->s.btp, tvals, tstride, g->s.D, g->s.E, g->s.L, neg, tproj);
+    op.cheb(Hs, D, Zs);
+    op.gemm(ar, Zs, M, 3 * D, s.wout, W + s.bout, y, s.cout, s.cout, dpkg::G_BIAS);
 }
 
 // One dpkg::qsample launch over N poses of pe floats (dpk_q_sample, and gen_sample's copy-in with the start on)
@@ -989,7 +930,7 @@ static int gen_sample(dpk_handle* h, Sched* sc, const float* x, float* out, floa
     GenModel* g = h->gen;
     const int K = sc->K;
     const long long n = (long long)N * g->s.J * g->s.cin;
-    const size_t act = gen_act_floats(g, N), tpf = (size_t)K * g->s.L * g->s.D;
+    const size_t act = gen_act_floats(g->s, N), tpf = (size_t)K * g->s.L * g->s.D;
     float* S = nullptr;
     int rc = gen_scratch(h, st, cap, act + 2 * (size_t)n + tpf, &S, "dpk_sample");
     if (rc) return rc;
@@ -997,9 +938,10 @@ static int gen_sample(dpk_handle* h, Sched* sc, const float* x, float* out, floa
     float* tproj = eps + n;
     float* xt = tproj + tpf;
     auto body = [&](hipStream_t s_, float* cur) {
-        gen_temb(g, s_, sc->coef + 5, 6, K, tproj);
+        const GenOps op(g, s_, N, h->mask, h->pmask, h->n_cu, g->forms);
+        op.temb(sc->coef + 5, 6, K, tproj);
         for (int s = 0; s < K; ++s) {
-            gen_forward(g, s_, cur, N, tproj + (size_t)s * g->s.L * g->s.D, 0, h->mask, h->pmask, eps, S, h->n_cu);
+            gen_forward(g, op, cur, tproj + (size_t)s * g->s.L * g->s.D, 0, eps, S);
             hipLaunchKernelGGL(dpkg::ddim, dim3(gen_blocks(n)), dim3(256), 0, s_, cur, eps, cur,
                                x0s ? x0s + (size_t)s * n : nullptr, n, sc->coef + s * 6, s, sc->eta,
                                (unsigned long long)seed, noise ? noise + (size_t)s * n : nullptr);
@@ -1087,23 +1029,21 @@ static void gen_diff_loss(hipStream_t st, const float* eps, int N, int pe, const
                        (unsigned long long)seed, loss);
 }
 
-// floats of scratch one gen_eps call over N poses takes: the forward's activations, then the per-pose projections
-static size_t gen_eps_floats(const GenModel* g, int N) { return gen_act_floats(g, N) + (size_t)N * g->s.L * g->s.D; }
-
 // dpk_eps on the generic path: per-pose timestep projections, one forward.  S: gen_eps_floats(N) floats of the
 // call's scratch, or null to take them here
 static int gen_eps(dpk_handle* h, const float* x, const float* t, float* eps, int N, hipStream_t st, bool cap,
                    float* S = nullptr) {
     GenModel* g = h->gen;
-    const size_t act = gen_act_floats(g, N);
+    const size_t act = gen_act_floats(g->s, N);
     if (!S) {
-        const int rc = gen_scratch(h, st, cap, gen_eps_floats(g, N), &S, "dpk_eps");
+        const int rc = gen_scratch(h, st, cap, gen_eps_floats(g->s, N), &S, "dpk_eps");
         if (rc) return rc;
     }
     float* tproj = S + act;
     return profiled(h, st, cap, "dpk_eps", [&]() -> int {
-        gen_temb(g, st, t, 1, N, tproj);
-        gen_forward(g, st, x, N, tproj, g->s.L * g->s.D, h->mask, h->pmask, eps, S, h->n_cu);
+        const GenOps op(g, st, N, h->mask, h->pmask, h->n_cu, g->forms);
+        op.temb(t, 1, N, tproj);
+        gen_forward(g, op, x, tproj, g->s.L * g->s.D, eps, S);
         HIPCHK(h, hipGetLastError());
         return DPK_OK;
     });
@@ -1113,13 +1053,13 @@ static int gen_eps(dpk_handle* h, const float* x, const float* t, float* eps, in
 static int gen_pose(dpk_handle* h, const float* x2d, float* xyz, float* uvxyz, int N, int Hn, int root_mode,
                     hipStream_t st, bool cap) {
     GenModel* g = h->gen;
-    const size_t act = gen_act_floats(g, N);
+    const size_t act = gen_act_floats(g->s, N);
     float* S = nullptr;
     const int rc = gen_scratch(h, st, cap, act + (size_t)N * g->s.J * g->s.cout, &S, "dpk_pose");
     if (rc) return rc;
     float* y = S + act;
     return profiled(h, st, cap, "dpk_pose", [&]() -> int {
-        gen_forward(g, st, x2d, N, nullptr, 0, h->mask, h->pmask, y, S, h->n_cu);
+        gen_forward(g, GenOps(g, st, N, h->mask, h->pmask, h->n_cu, g->forms), x2d, nullptr, 0, y, S);
         hipLaunchKernelGGL(dpkg::pose_out, dim3(gen_blocks((long long)N * g->s.J * (g->s.cin + g->s.cout))), dim3(256), 0,
                            st, x2d, y, N, g->s.J, g->s.cin, g->s.cout, xyz, uvxyz, Hn, root_mode);
         HIPCHK(h, hipGetLastError());

@@ -1,10 +1,10 @@
 // dpk_generic_bwd.inc — the gradient of the denoising objective (dpk_diff_loss_grad) on the per-op path: the
 // forward of dpk_generic.inc run once more with what the backward needs kept in the call's scratch, then the
 // backward as per-op HIP kernels, fp32 throughout, eval mode (no dropout).  Included by dpk_kernels.hip after
-// dpk_generic.inc and dpk_grad_layout.inc.
-//   training forward  gen_forward's launches (the same kernels and form choices, out of place), every GEMM operand,
+// dpk_generic.inc and dpk_grad_layout.inc; forms, grids and LDS sizes come from dpk_genplan.inc.
+//   training forward  gen_forward's ops (GenOps: the same kernels and form choices, out of place), every GEMM operand,
 //                     ReLU output and residual-stream value of every layer stored (bwd_plan: the stash)
-//   dX GEMMs          dA = dC W^T on gemm / gemm_sk / gemm_narrow against the transposed arena (BwdArena)
+//   dX GEMMs          dA = dC W^T, GenOps::gemm against the transposed arena (BwdArena)
 //   dW GEMMs          dW = A^T dC: dw_partial, one [K][N] slab per DW_ROWS rows on v_mfma_f32_16x16x4_f32, the bias
 //                     gradient (column sums) as row K of the slab; dw_reduce adds the slabs in
 //                     ascending order and writes the torch layout (transposed for nn.Linear, QKV split in three)
@@ -14,24 +14,6 @@
 // and an ordered sum pass: no float atomics, so the same call gives bitwise the same gradients.
 
 namespace dpkg {
-
-constexpr int DW_ROWS = 128;     // rows of one dW slab
-constexpr int DLG_POSES = 8;     // poses of one dL_g slab
-
-// the backward's kernel forms, one bit each (dpk_debug_grad_forms; diffpose_amd/gcndiff.py GRAD_FORMS)
-enum BwdForm : unsigned {
-    B_DW_VEC = 1u << 0,
-    B_DW_SCALAR = 1u << 1,
-    B_ATTN_BWD_STAGED = 1u << 2,
-    B_LN_BWD = 1u << 3,
-    B_GRAPH_T_STAGED = 1u << 4,
-    B_GRAPH_T_GLOBAL = 1u << 5,
-    B_CHEB_T = 1u << 6,
-    B_DLG_STAGED = 1u << 7,
-    B_TEMB_BWD = 1u << 8,
-    B_ATTN_BWD_GLOBAL = 1u << 9,
-    B_DLG_GLOBAL = 1u << 10,
-};
 
 // P[slab][k][n] = sum over the slab's rows r (ascending, four at a time) of A[r][k] G[r][n]; slab s holds rows
 // DW_ROWS s .. ; slab stride `ps` floats ((K + 1) N: row K is the column sum of G over the slab's rows, the bias
@@ -462,60 +444,6 @@ __global__ void __launch_bounds__(256) loss_grad(const float* __restrict__ eps, 
     dEps[g] = -2.0f * weight * (target - eps[g]);
 }
 
-// temb with what its backward reads kept: emb [D], the pre-activations u0, u1 and the activations h0, h1 [E] per
-// pose; the arithmetic of temb (tproj is bitwise its)
-__global__ void __launch_bounds__(256) temb_train(const float* __restrict__ W0, const float* __restrict__ B0,
-                                                  const float* __restrict__ W1, const float* __restrict__ B1,
-                                                  const float* __restrict__ WP, const float* __restrict__ BP,
-                                                  const float* __restrict__ tvals, int D, int E, int L, float neg_scale,
-                                                  float* __restrict__ tproj, float* __restrict__ emb_o,
-                                                  float* __restrict__ u0_o, float* __restrict__ h0_o,
-                                                  float* __restrict__ u1_o, float* __restrict__ h1_o) {
-    extern __shared__ float ttsm[];
-    float* emb = ttsm;
-    float* h0 = ttsm + D;
-    float* h1 = h0 + E;
-    const size_t b = blockIdx.x;
-    const float t = tvals[b];
-    const int half = D / 2;
-    for (int i = threadIdx.x; i < D; i += 256) {
-        float v = 0.f;
-        if (i < 2 * half) {
-            const int k = i < half ? i : i - half;
-            const float arg = t * expf((float)k * neg_scale);
-            v = i < half ? sinf(arg) : cosf(arg);
-        }
-        emb[i] = v;
-        emb_o[b * D + i] = v;
-    }
-    __syncthreads();
-    for (int o = threadIdx.x; o < E; o += 256) {
-        float acc = 0.f;
-        for (int k = 0; k < D; ++k) acc = fmaf(emb[k], W0[(size_t)k * E + o], acc);
-        const float v = acc + B0[o];
-        h0[o] = v * (1.0f / (1.0f + expf(-v)));
-        u0_o[b * E + o] = v;
-        h0_o[b * E + o] = h0[o];
-    }
-    __syncthreads();
-    for (int o = threadIdx.x; o < E; o += 256) {
-        float acc = 0.f;
-        for (int k = 0; k < E; ++k) acc = fmaf(h0[k], W1[(size_t)k * E + o], acc);
-        const float v = acc + B1[o];
-        h1[o] = v * (1.0f / (1.0f + expf(-v)));
-        u1_o[b * E + o] = v;
-        h1_o[b * E + o] = h1[o];
-    }
-    __syncthreads();
-    for (int o = threadIdx.x; o < L * D; o += 256) {
-        const int l = o / D, c = o - l * D;
-        const float* wp = WP + (size_t)l * E * D;
-        float acc = 0.f;
-        for (int k = 0; k < E; ++k) acc = fmaf(h1[k], wp[(size_t)k * D + c], acc);
-        tproj[b * L * D + o] = acc + BP[o];
-    }
-}
-
 }  // namespace dpkg
 
 // ---------------------------------------------------------------------------------------
@@ -526,12 +454,7 @@ struct BwdModel {
     GenModel* own = nullptr;     // a persistent-sampler handle's per-op model (a per-op handle uses its own)
     GradLayout lay;
     BwdArena arena;
-    float* dev = nullptr;        // device: the transposed arena
-    size_t dev_floats = 0;
-    std::vector<GenPack> packs;  // gemm_sk copies of its GEMM blocks
-    std::vector<float> hp;
-    float* devp = nullptr;
-    size_t devp_floats = 0;
+    GemmArena dev;               // the transposed arena on the device, with the gemm_sk copies of its GEMM blocks
     uint64_t serial = 0;         // dpk_handle::stage_serial it was built from (0: never)
     unsigned fforms = 0, bforms = 0;   // GenForm bits of the forward and dX launches; BwdForm bits
 };
@@ -539,141 +462,8 @@ struct BwdModel {
 static void bwd_free(BwdModel* b) {
     if (!b) return;
     gen_free(b->own);
-    if (b->dev) (void)hipFree(b->dev);
-    if (b->devp) (void)hipFree(b->devp);
+    b->dev.free();
     delete b;
-}
-
-// gemm_sk's fragment order for the transposed blocks (gen_pack's rule and layout)
-static void bwd_pack(BwdModel* b) {
-    b->packs.clear();
-    size_t off = 0;
-    for (const BwdBlock& k : b->arena.blocks) {
-        const int K = k.N, N = k.K;      // the transposed block is [N][K] of the forward's
-        if (K % 4 || N % 4 || N <= 8) continue;
-        const int NT16 = (N + 15) / 16, NJ = NT16 % 4 == 0 ? 4 : 2, NTp = (NT16 + NJ - 1) / NJ * NJ;
-        b->packs.push_back(GenPack{k.w, off, K, N, NJ});
-        off += (size_t)((K + 15) / 16) * NTp * 256;
-    }
-    b->hp.assign(off, 0.f);
-    for (const GenPack& p : b->packs) {
-        const int KC = (p.K + 15) / 16, NT16 = (p.N + 15) / 16, NTp = (NT16 + p.NJ - 1) / p.NJ * p.NJ;
-        const float* W = b->arena.h.data() + p.w;
-        float* dst = b->hp.data() + p.off;
-        for (int c = 0; c < KC; ++c)
-            for (int t = 0; t < NT16; ++t)
-                for (int l = 0; l < 64; ++l)
-                    for (int s = 0; s < 4; ++s) {
-                        const int k = 16 * c + 4 * (l >> 4) + s, n = 16 * t + (l & 15);
-                        if (k < p.K && n < p.N) dst[(((size_t)c * NTp + t) * 64 + l) * 4 + s] = W[(size_t)k * p.N + n];
-                    }
-    }
-}
-
-// One GEMM C = epilogue(A[M][K] W[K][N] + bias) in the form gen_forward's rule picks (the same predicates): W, bias
-// device pointers, pk its gemm_sk copy or null
-static void bwd_gemm(unsigned& forms, hipStream_t st, int n_cu, int J, const float* a, int M, int K, const float* W,
-                     const GenPack* pk, const float* devp, const float* bias, float* c, int ldc, int Nn, int mode,
-                     const float* tpl = nullptr, int tps = 0) {
-    const long long nt = (Nn + dpkg::GBN - 1) / dpkg::GBN, cu = std::max(n_cu, 1);
-    int bm = 128;
-    long long best = -1;
-    for (int cand : {128, 64, 32}) {
-        const long long cost = ((M + cand - 1) / cand * nt + cu - 1) / cu * cand;
-        if (best < 0 || cost < best) best = cost, bm = cand;
-    }
-    const dim3 grid((unsigned)((M + bm - 1) / bm), (unsigned)nt);
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    const bool vec = K % 4 == 0 && Nn % 4 == 0 && al16(a) && al16(W);
-    if (Nn <= 8 && (size_t)K * Nn * 4 <= 65536) {
-        forms |= dpkg::F_GEMM_NARROW;
-        hipLaunchKernelGGL(dpkg::gemm_narrow, dim3((unsigned)((M + 3) / 4)), dim3(256), (size_t)K * Nn * 4, st, a, K, W, bias,
-                           c, ldc, M, Nn, K, mode, tpl, tps, J);
-        return;
-    }
-    if (pk && vec && ldc % 4 == 0 && al16(c) && al16(bias) && (!tpl || (al16(tpl) && tps % 4 == 0)) &&
-        (size_t)M * K * 4 + (size_t)K * 4 < dpkg::SK_OOR) {
-        const dim3 gs((unsigned)((M + 15) / 16), (unsigned)(((Nn + 15) / 16 + pk->NJ - 1) / pk->NJ));
-        forms |= pk->NJ == 4 ? dpkg::F_GEMM_SK4 : dpkg::F_GEMM_SK2;
-        if (pk->NJ == 4)
-            hipLaunchKernelGGL(dpkg::gemm_sk<4>, gs, dim3(256), 0, st, a, K, devp + pk->off, bias, c, ldc, M, Nn, K, mode,
-                               tpl, tps, J);
-        else
-            hipLaunchKernelGGL(dpkg::gemm_sk<2>, gs, dim3(256), 0, st, a, K, devp + pk->off, bias, c, ldc, M, Nn, K, mode,
-                               tpl, tps, J);
-        return;
-    }
-#define DPKG_GEMM(BM_, V_) hipLaunchKernelGGL((dpkg::gemm<BM_, V_>), grid, dim3(256), 0, st, a, K, W, bias, c, ldc, M, Nn, K, mode, tpl, tps, J)
-    if (bm == 128) {
-        forms |= vec ? dpkg::F_GEMM_128_VEC : dpkg::F_GEMM_128_SCALAR;
-        if (vec) DPKG_GEMM(128, true);
-        else DPKG_GEMM(128, false);
-    } else if (bm == 64) {
-        forms |= vec ? dpkg::F_GEMM_64_VEC : dpkg::F_GEMM_64_SCALAR;
-        if (vec) DPKG_GEMM(64, true);
-        else DPKG_GEMM(64, false);
-    } else {
-        forms |= vec ? dpkg::F_GEMM_32_VEC : dpkg::F_GEMM_32_SCALAR;
-        if (vec) DPKG_GEMM(32, true);
-        else DPKG_GEMM(32, false);
-    }
-#undef DPKG_GEMM
-}
-
-static const GenPack* find_pack(const std::vector<GenPack>& packs, size_t w, int K, int N) {
-    for (const GenPack& p : packs)
-        if (p.w == w && p.K == K && p.N == N) return &p;
-    return nullptr;
-}
-
-// The call's scratch, in floats, every part on a 256-byte boundary.  Per layer the stash keeps 22 D floats a row
-// (H, Y0, QKV 3D, A, H1, Y1, G1, F 2D, G2 2D, H2, Z1 3D, R1, Z2 3D, R2); beside the layers 3 cin + 4 D a row (the
-// input's and the output's Chebyshev operands, the last H), and D + 4 E + L D floats a pose for the timestep MLP:
-//   stash(N) = N J (22 D L + 4 D + 3 cin) + N (D + 4 E + L D)
-// then the backward's working set: 10 D + 2 cout + cin floats a row, 2 E + L D a pose, the dW slabs and dL_g slabs.
-struct BwdLayerBufs {
-    float *H, *Y0, *QKV, *A, *H1, *Y1, *G1, *F, *G2, *H2, *Z1, *R1, *Z2, *R2;
-};
-struct BwdPlan {
-    std::vector<BwdLayerBufs> lay;
-    float *xt, *eps, *dEps, *Z0, *Hlast, *Zout, *C1;
-    float *tproj, *dtp, *emb, *u0, *h0, *u1, *h1, *dh, *du;
-    float *dH, *tD1, *tD2, *t3D, *t2Da, *t2Db, *Pdw, *Plg;
-    size_t pdw_floats, stash_floats, floats;
-};
-static BwdPlan bwd_plan(const Stage& s, int N, float* base) {
-    BwdPlan p;
-    const size_t M = (size_t)N * s.J, D = s.D, E = s.E, L = s.L;
-    size_t o = 0;
-    auto take = [&](size_t n) {
-        float* at = base + o;      // base null: sizes only
-        o += (n + 63) / 64 * 64;
-        return at;
-    };
-    p.lay.resize(L);
-    p.Z0 = take(M * 3 * s.cin);
-    for (auto& b : p.lay) {
-        b.H = take(M * D), b.Y0 = take(M * D), b.QKV = take(M * 3 * D), b.A = take(M * D), b.H1 = take(M * D);
-        b.Y1 = take(M * D), b.G1 = take(M * D), b.F = take(M * 2 * D), b.G2 = take(M * 2 * D), b.H2 = take(M * D);
-        b.Z1 = take(M * 3 * D), b.R1 = take(M * D), b.Z2 = take(M * 3 * D), b.R2 = take(M * D);
-    }
-    p.Hlast = take(M * D), p.Zout = take(M * 3 * D);
-    p.tproj = take((size_t)N * L * D), p.emb = take((size_t)N * D);
-    p.u0 = take((size_t)N * E), p.h0 = take((size_t)N * E), p.u1 = take((size_t)N * E), p.h1 = take((size_t)N * E);
-    p.stash_floats = o;
-    p.xt = take(M * s.cin), p.eps = take(M * s.cout), p.dEps = take(M * s.cout), p.C1 = take(M * D);
-    p.dtp = take((size_t)N * L * D), p.dh = take((size_t)N * E), p.du = take((size_t)N * E);
-    p.dH = take(M * D), p.tD1 = take(M * D), p.tD2 = take(M * D), p.t3D = take(M * 3 * D);
-    p.t2Da = take(M * 2 * D), p.t2Db = take(M * 2 * D);
-    // the dW slabs: (K + 1) N floats per DW_ROWS rows, the largest of the row GEMMs (M rows) and the MLP's (N rows)
-    const size_t sm = (M + dpkg::DW_ROWS - 1) / dpkg::DW_ROWS, sn = ((size_t)N + dpkg::DW_ROWS - 1) / dpkg::DW_ROWS;
-    const size_t kn_rows = std::max(std::max((3 * D + 1) * D, (D + 1) * 3 * D),
-                                    std::max((3 * (size_t)s.cin + 1) * D, (3 * D + 1) * (size_t)s.cout));
-    p.pdw_floats = std::max(sm * kn_rows, sn * (E + 1) * E);
-    p.Pdw = take(p.pdw_floats);
-    p.Plg = take(2 * (((size_t)N + dpkg::DLG_POSES - 1) / dpkg::DLG_POSES) * s.J * s.J);
-    p.floats = o;
-    return p;
 }
 
 // (Re)build what the handle keeps for the backward: the per-op model of a persistent-sampler handle, the parameter
@@ -691,21 +481,10 @@ static int bwd_prepare(dpk_handle* h) {
     HIPCHK(h, hipDeviceSynchronize());
     b->lay = grad_layout(h->stage);
     bwd_arena_build(h->stage, b->arena);
-    bwd_pack(b);
-    if (b->dev_floats < b->arena.floats) {
-        if (b->dev) HIPCHK(h, hipFree(b->dev));
-        b->dev = nullptr, b->dev_floats = 0;
-        HIPCHK(h, hipMalloc(&b->dev, b->arena.floats * 4));
-        b->dev_floats = b->arena.floats;
-    }
-    HIPCHK(h, hipMemcpy(b->dev, b->arena.h.data(), b->arena.floats * 4, hipMemcpyHostToDevice));
-    if (b->devp_floats < b->hp.size()) {
-        if (b->devp) HIPCHK(h, hipFree(b->devp));
-        b->devp = nullptr, b->devp_floats = 0;
-        HIPCHK(h, hipMalloc(&b->devp, b->hp.size() * 4));
-        b->devp_floats = b->hp.size();
-    }
-    if (!b->hp.empty()) HIPCHK(h, hipMemcpy(b->devp, b->hp.data(), b->hp.size() * 4, hipMemcpyHostToDevice));
+    std::vector<PackBlock> blocks;       // the transposed block is [N][K] of the forward's
+    for (const BwdBlock& k : b->arena.blocks) blocks.push_back({k.w, k.N, k.K});
+    const int rc = b->dev.upload(h, b->arena.h.data(), b->arena.floats, blocks);
+    if (rc) return rc;
     b->serial = h->stage_serial;
     return DPK_OK;
 }
@@ -723,91 +502,50 @@ static int bwd_run(dpk_handle* h, const float* x0, const float* t, const StartSp
     int rc = gen_scratch(h, st, false, need, &S, "dpk_diff_loss_grad");
     if (rc) return rc;
     const BwdPlan p = bwd_plan(s, N, S);
-    const float* W = g->dev;             // the forward's arena
-    const float* WT = b->dev;            // the transposed arena
+    const GemmArena& ar = g->arena;      // the forward's arena
+    const float* W = ar.dev;
+    const float* WT = b->dev.dev;        // the transposed arena
     const float* zero = WT + b->arena.zero;
     const GradLayout& gl = b->lay;
-    const int n_cu = h->n_cu;
-    const unsigned mask = h->mask;
-    const unsigned* pmask = h->pmask;
+    const GenOps op(g, st, N, h->mask, h->pmask, h->n_cu, b->fforms);
     auto blocks = [](long long n) { return dim3(gen_blocks(n)); };
-    auto fwd_gemm = [&](const float* a, int K, size_t w, size_t bias, float* c, int Nn, int mode) {
-        bwd_gemm(b->fforms, st, n_cu, J, a, M, K, W + w, find_pack(g->packs, w, K, Nn), g->devp, W + bias, c, Nn, Nn, mode);
-    };
-    auto cheb = [&](const float* xin, int C, float* Z) {
-        const size_t lds = ((size_t)J * C + 2 * J * J) * 4;
-        b->fforms |= lds <= 65536 ? dpkg::F_CHEB_T : dpkg::F_CHEB_F;
-        if (lds <= 65536)
-            hipLaunchKernelGGL(dpkg::cheb_basis<true>, dim3((unsigned)N), dim3(256), lds, st, W + s.t1, W + s.t2, xin, Z, N, J, C);
-        else
-            hipLaunchKernelGGL(dpkg::cheb_basis<false>, blocks((long long)M * C), dim3(256), 0, st, W + s.t1, W + s.t2, xin, Z,
-                               N, J, C);
-    };
-    // Y = Lm X with Lm the layer's Laplacian (forward) or its transpose (backward)
-    auto graph = [&](const float* Lm, const float* xin, int C, float* yout, bool back) {
-        const size_t lds = ((size_t)J * C + J * J) * 4;
-        if (back) b->bforms |= lds <= 65536 ? dpkg::B_GRAPH_T_STAGED : dpkg::B_GRAPH_T_GLOBAL;
-        else b->fforms |= lds <= 65536 ? dpkg::F_GRAPH_T : dpkg::F_GRAPH_F;
-        if (lds <= 65536)
-            hipLaunchKernelGGL(dpkg::graph<true>, dim3((unsigned)N), dim3(256), lds, st, Lm, xin, C, yout, C, N, J, C);
-        else
-            hipLaunchKernelGGL(dpkg::graph<false>, blocks((long long)M * C), dim3(256), 0, st, Lm, xin, C, yout, C, N, J, C);
-    };
     auto copy = [&](float* dst, const float* src, size_t n) {
         return hipMemcpyAsync(dst, src, n * 4, hipMemcpyDeviceToDevice, st);
     };
 
-    // ---- noising and the training forward
+    // ---- noising and the training forward: gen_forward's ops, to be read beside it.  The two sequences stay two:
+    // this one keeps every intermediate in a buffer of its own and leaves relu + temb and resid + relu out of the
+    // GEMM epilogues (add_temb, add2), since the backward reads R1 and R2.
     gen_qsample_t(st, x0, p.xt, N, pe, t, sc->qtab, sc->nt, spec, seed);
-    {
-        const int half = D / 2;
-        const float neg = -(float)(log(10000.0) / (double)(half - 1));
-        hipLaunchKernelGGL(dpkg::temb_train, dim3((unsigned)N), dim3(256), (size_t)(D + 2 * E) * 4, st, W + s.d0w, W + s.d0b,
-                           W + s.d1w, W + s.d1b, W + s.wtp, W + s.btp, t, D, E, L, neg, p.tproj, p.emb, p.u0, p.h0, p.u1,
-                           p.h1);
-    }
-    cheb(p.xt, cin, p.Z0);
-    fwd_gemm(p.Z0, 3 * cin, s.win, s.bin, p.lay.empty() ? p.Hlast : p.lay[0].H, D, dpkg::G_BIAS);
+    const dpkg::TembStash keep{p.emb, p.u0, p.h0, p.u1, p.h1};
+    op.temb(t, 1, N, p.tproj, &keep);
+    op.cheb(p.xt, cin, p.Z0);
+    op.gemm(ar, p.Z0, M, 3 * cin, s.win, W + s.bin, p.lay.empty() ? p.Hlast : p.lay[0].H, D, D, dpkg::G_BIAS);
     for (int l = 0; l < L; ++l) {
         const GenLayer& o = s.lay[l];
         const BwdLayerBufs& y = p.lay[l];
         float* Hnext = l + 1 < L ? p.lay[l + 1].H : p.Hlast;
-        hipLaunchKernelGGL(dpkg::layer_norm, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, y.H, y.Y0, M, D, W + o.n0a,
-                           W + o.n0b);
-        fwd_gemm(y.Y0, D, o.wqkv, o.bqkv, y.QKV, 3 * D, dpkg::G_BIAS);
-        const bool avec = (D / s.H) % 4 == 0 && D % 8 == 0;      // every buffer of the plan is 256-byte aligned
-        const size_t pose_bytes = (size_t)J * (3 * D + (avec ? 4 : 1)) * 4;
-        const int ppb = std::max(1, std::min(256 / (s.H * J), (int)(65536 / pose_bytes)));
-        const unsigned ab = (unsigned)((N + ppb - 1) / ppb);
-        b->fforms |= pose_bytes > 65536 ? dpkg::F_ATTENTION_FF : avec ? dpkg::F_ATTENTION_TT : dpkg::F_ATTENTION_TF;
-        if (pose_bytes > 65536)
-            hipLaunchKernelGGL((dpkg::attention<false, false>), dim3((unsigned)N), dim3(256), 0, st, y.QKV, y.A, N, J, D, s.H,
-                               mask, pmask, 1);
-        else if (avec)
-            hipLaunchKernelGGL((dpkg::attention<true, true>), dim3(ab), dim3(256), pose_bytes * ppb, st, y.QKV, y.A, N, J, D,
-                               s.H, mask, pmask, ppb);
-        else
-            hipLaunchKernelGGL((dpkg::attention<true, false>), dim3(ab), dim3(256), pose_bytes * ppb, st, y.QKV, y.A, N, J, D,
-                               s.H, mask, pmask, ppb);
+        op.layer_norm(y.H, y.Y0, o.n0a, o.n0b);
+        op.gemm(ar, y.Y0, M, D, o.wqkv, W + o.bqkv, y.QKV, 3 * D, 3 * D, dpkg::G_BIAS);
+        op.attention(y.QKV, y.A);
         HIPCHK(h, copy(y.H1, y.H, (size_t)M * D));
-        fwd_gemm(y.A, D, o.wo, o.bo, y.H1, D, dpkg::G_RESID);
-        hipLaunchKernelGGL(dpkg::layer_norm, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, y.H1, y.Y1, M, D, W + o.n1a,
-                           W + o.n1b);
-        graph(W + o.lg, y.Y1, D, y.G1, false);
-        fwd_gemm(y.G1, D, o.w1, o.b1, y.F, 2 * D, dpkg::G_RELU);
-        graph(W + o.lg, y.F, 2 * D, y.G2, false);
+        op.gemm(ar, y.A, M, D, o.wo, W + o.bo, y.H1, D, D, dpkg::G_RESID);
+        op.layer_norm(y.H1, y.Y1, o.n1a, o.n1b);
+        op.graph(W + o.lg, y.Y1, D, y.G1);
+        op.gemm(ar, y.G1, M, D, o.w1, W + o.b1, y.F, 2 * D, 2 * D, dpkg::G_RELU);
+        op.graph(W + o.lg, y.F, 2 * D, y.G2);
         HIPCHK(h, copy(y.H2, y.H1, (size_t)M * D));
-        fwd_gemm(y.G2, 2 * D, o.w2, o.b2, y.H2, D, dpkg::G_RESID);
-        cheb(y.H2, D, y.Z1);
-        fwd_gemm(y.Z1, 3 * D, o.wc1, o.bc1, y.R1, D, dpkg::G_RELU);
+        op.gemm(ar, y.G2, M, 2 * D, o.w2, W + o.b2, y.H2, D, D, dpkg::G_RESID);
+        op.cheb(y.H2, D, y.Z1);
+        op.gemm(ar, y.Z1, M, 3 * D, o.wc1, W + o.bc1, y.R1, D, D, dpkg::G_RELU);
         hipLaunchKernelGGL(dpkg::add_temb, blocks((long long)M * D), dim3(256), 0, st, y.R1, p.tproj + (size_t)l * D, L * D,
                            p.C1, (long long)M * D, D, J);
-        cheb(p.C1, D, y.Z2);
-        fwd_gemm(y.Z2, 3 * D, o.wc2, o.bc2, y.R2, D, dpkg::G_RELU);
+        op.cheb(p.C1, D, y.Z2);
+        op.gemm(ar, y.Z2, M, 3 * D, o.wc2, W + o.bc2, y.R2, D, D, dpkg::G_RELU);
         hipLaunchKernelGGL(dpkg::add2, blocks((long long)M * D), dim3(256), 0, st, y.H2, y.R2, Hnext, (long long)M * D);
     }
-    cheb(p.Hlast, D, p.Zout);
-    fwd_gemm(p.Zout, 3 * D, s.wout, s.bout, p.eps, cout, dpkg::G_BIAS);
+    op.cheb(p.Hlast, D, p.Zout);
+    op.gemm(ar, p.Zout, M, 3 * D, s.wout, W + s.bout, p.eps, cout, cout, dpkg::G_BIAS);
     if (loss) gen_diff_loss(st, p.eps, N, pe, spec, seed, loss);
     HIPCHK(h, hipGetLastError());
 
@@ -816,22 +554,12 @@ static int bwd_run(dpk_handle* h, const float* x0, const float* t, const StartSp
     // dW = A^T G over `rows` rows into the layout (see dw_reduce)
     auto dW = [&](const float* A, int lda, int rows, int K, const float* G, int ldg, int Nn, bool transpose, int Ns,
                   dpkg::DwDst dst) {
-        const unsigned nslab = (unsigned)((rows + dpkg::DW_ROWS - 1) / dpkg::DW_ROWS);
-        const size_t ps = (size_t)(K + 1) * Nn;
-        auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-        const bool vec = K % 4 == 0 && Nn % 4 == 0 && lda % 4 == 0 && ldg % 4 == 0 && al16(A) && al16(G) && al16(p.Pdw);
-        if (vec) {
-            b->bforms |= dpkg::B_DW_VEC;
-            const unsigned tiles = (unsigned)(((K + 63) / 64) * ((Nn + 63) / 64));
-            hipLaunchKernelGGL(dpkg::dw_partial<true>, dim3(nslab, (tiles + 3) / 4), dim3(256), 0, st, A, lda, G, ldg, p.Pdw, ps,
-                               rows, K, Nn);
-        } else {
-            b->bforms |= dpkg::B_DW_SCALAR;
-            const unsigned tiles = (unsigned)(((K + 15) / 16) * ((Nn + 31) / 32));
-            hipLaunchKernelGGL(dpkg::dw_partial<false>, dim3(nslab, (tiles + 3) / 4), dim3(256), 0, st, A, lda, G, ldg, p.Pdw,
-                               ps, rows, K, Nn);
-        }
-        hipLaunchKernelGGL(dpkg::dw_reduce, blocks((long long)(K + 1) * Nn), dim3(256), 0, st, p.Pdw, ps, (int)nslab, K, Nn,
+        const auto at = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
+        const DwChoice d = dw_choice(rows, K, Nn, lda, ldg, at(A), at(G), at(p.Pdw));
+        b->bforms |= d.vec ? dpkg::B_DW_VEC : dpkg::B_DW_SCALAR;
+        auto* kernel = d.vec ? dpkg::dw_partial<true> : dpkg::dw_partial<false>;
+        hipLaunchKernelGGL(kernel, dim3(d.nslab, d.gy), dim3(256), 0, st, A, lda, G, ldg, p.Pdw, d.ps, rows, K, Nn);
+        hipLaunchKernelGGL(dpkg::dw_reduce, blocks((long long)(K + 1) * Nn), dim3(256), 0, st, p.Pdw, d.ps, (int)d.nslab, K, Nn,
                            transpose ? 1 : 0, Ns, dst);
     };
     auto one = [&](size_t w, size_t bias) { return dpkg::DwDst{{grads + w, nullptr, nullptr}, {grads + bias, nullptr, nullptr}}; };
@@ -845,8 +573,7 @@ static int bwd_run(dpk_handle* h, const float* x0, const float* t, const StartSp
     };
     // dA [rows][Kf] = G [rows][Nf] W^T for the forward block W [Kf][Nf] at arena offset w
     auto dX = [&](const float* G, int rows, int Nf, size_t w, int Kf, float* out) {
-        bwd_gemm(b->fforms, st, n_cu, J, G, rows, Nf, WT + w, find_pack(b->packs, w, Nf, Kf), b->devp, zero, out, Kf, Kf,
-                 dpkg::G_BIAS);
+        op.gemm(b->dev, G, rows, Nf, w, zero, out, Kf, Kf, dpkg::G_BIAS);
     };
     auto cheb_t = [&](const float* dZ, float* dXo, bool acc) {
         b->bforms |= dpkg::B_CHEB_T;
@@ -862,14 +589,12 @@ static int bwd_run(dpk_handle* h, const float* x0, const float* t, const StartSp
         dvec(p.tD1, M, D, da);
         dvec(dY, M, D, db);
     };
-    const unsigned lgslabs = (unsigned)((N + dpkg::DLG_POSES - 1) / dpkg::DLG_POSES);
+    const unsigned lgslabs = dlg_choice(N, J, D).blocks;
     auto dlg = [&](const float* dY, const float* X, int C, float* P) {
-        const size_t lds = (size_t)2 * J * (C | 1) * 4;
-        b->bforms |= lds <= 65536 ? dpkg::B_DLG_STAGED : dpkg::B_DLG_GLOBAL;
-        if (lds <= 65536)
-            hipLaunchKernelGGL(dpkg::dlg_partial<true>, dim3(lgslabs), dim3(256), lds, st, dY, X, P, N, J, C);
-        else
-            hipLaunchKernelGGL(dpkg::dlg_partial<false>, dim3(lgslabs), dim3(256), 0, st, dY, X, P, N, J, C);
+        const StageChoice c = dlg_choice(N, J, C);
+        b->bforms |= c.stage ? dpkg::B_DLG_STAGED : dpkg::B_DLG_GLOBAL;
+        auto* kernel = c.stage ? dpkg::dlg_partial<true> : dpkg::dlg_partial<false>;
+        hipLaunchKernelGGL(kernel, dim3(c.blocks), dim3(256), c.lds, st, dY, X, P, N, J, C);
     };
     const long long MD = (long long)M * D;
 
@@ -898,12 +623,12 @@ static int bwd_run(dpk_handle* h, const float* x0, const float* t, const StartSp
         dW(y.G2, 2 * D, M, 2 * D, p.dH, D, D, true, D, one(q.f2w, q.f2b));
         dX(p.dH, M, D, o.w2, 2 * D, p.t2Da);         // dG2
         dlg(p.t2Da, y.F, 2 * D, p.Plg + (size_t)lgslabs * J * J);
-        graph(WT + o.lg, p.t2Da, 2 * D, p.t2Db, true);    // dF
+        op.graph(WT + o.lg, p.t2Da, 2 * D, p.t2Db, &b->bforms);    // dF
         relu_bwd(p.t2Db, y.F, p.t2Da, 2 * MD);
         dW(y.G1, D, M, D, p.t2Da, 2 * D, 2 * D, true, 2 * D, one(q.f1w, q.f1b));
         dX(p.t2Da, M, 2 * D, o.w1, D, p.tD1);        // dG1
         dlg(p.tD1, y.Y1, D, p.Plg);
-        graph(WT + o.lg, p.tD1, D, p.tD2, true);     // dY1
+        op.graph(WT + o.lg, p.tD1, D, p.tD2, &b->bforms);     // dY1
         hipLaunchKernelGGL(dpkg::dlg_chain, dim3(1), dim3(256), (size_t)(J * J + 2 * J) * 4, st, p.Plg, (int)(2 * lgslabs),
                            WT + b->arena.ahat + (size_t)l * b->arena.jj4, grads + q.ahat, J);
         ln_bwd(y.H1, p.tD2, o.n1a, q.n1a, q.n1b);
@@ -911,12 +636,10 @@ static int bwd_run(dpk_handle* h, const float* x0, const float* t, const StartSp
         dW(y.A, D, M, D, p.dH, D, D, true, D, one(q.lw[3], q.lb[3]));
         dX(p.dH, M, D, o.wo, D, p.tD1);              // dA
         {
-            const int hb = std::max(1, std::min(std::min(s.H, 256 / J), 4096 / (J * J)));
-            const size_t ps_lds = (size_t)2 * hb * J * J * 4, staged = ps_lds + (size_t)J * ((4 * D) | 1) * 4;
-            const bool stage = staged <= 65536;
-            b->bforms |= stage ? dpkg::B_ATTN_BWD_STAGED : dpkg::B_ATTN_BWD_GLOBAL;
-            hipLaunchKernelGGL(dpkg::attention_bwd, dim3((unsigned)N), dim3(256), stage ? staged : ps_lds, st, y.QKV, p.tD1,
-                               p.t3D, J, D, s.H, mask, pmask, hb, stage ? 1 : 0);
+            const AttnBwdChoice a = attention_bwd_choice(J, D, s.H);
+            b->bforms |= a.stage ? dpkg::B_ATTN_BWD_STAGED : dpkg::B_ATTN_BWD_GLOBAL;
+            hipLaunchKernelGGL(dpkg::attention_bwd, dim3((unsigned)N), dim3(256), a.lds, st, y.QKV, p.tD1, p.t3D, J, D, s.H,
+                               h->mask, h->pmask, a.hb, a.stage ? 1 : 0);
         }
         dW(y.Y0, D, M, D, p.t3D, 3 * D, 3 * D, true, D,
            dpkg::DwDst{{grads + q.lw[0], grads + q.lw[1], grads + q.lw[2]}, {grads + q.lb[0], grads + q.lb[1], grads + q.lb[2]}});
@@ -928,7 +651,7 @@ static int bwd_run(dpk_handle* h, const float* x0, const float* t, const StartSp
     b->bforms |= dpkg::B_TEMB_BWD;
     for (int l = 0; l < L; ++l)
         dW(p.h1, E, N, E, p.dtp + (size_t)l * D, L * D, D, true, D, one(gl.lay[l].tpw, gl.lay[l].tpb));
-    bwd_gemm(b->fforms, st, n_cu, J, p.dtp, N, L * D, WT + s.wtp, nullptr, nullptr, zero, p.dh, E, E, dpkg::G_BIAS);
+    op.gemm(b->dev, p.dtp, N, L * D, s.wtp, zero, p.dh, E, E, dpkg::G_BIAS, nullptr, 0, false);
     hipLaunchKernelGGL(dpkg::swish_bwd, blocks((long long)N * E), dim3(256), 0, st, p.dh, p.u1, p.du, (long long)N * E);
     dW(p.h0, E, N, E, p.du, E, E, true, E, one(gl.d1w, gl.d1b));
     dX(p.du, N, E, s.d1w, E, p.dh);

@@ -144,6 +144,7 @@ static thread_local uint32_t last_kernel = KERNEL_NONE;
 }  // namespace dpk_shared
 
 #include "dpk_stage.inc"
+#include "dpk_genplan.inc"
 #include "dpk_scratch.inc"
 
 // All the host knows a compiled sampler instance by: its shape half (dpk_stage.inc) and how to launch it.  One
@@ -1343,7 +1344,7 @@ int dpk_diff_loss(dpk_handle* h, const float* x0, const float* t, const float* s
     const int pe = h->gen ? h->gen->s.J * h->gen->s.cin : h->n_pts * CIN;
     const auto up64 = [](size_t v) { return (v + 63) / 64 * 64; };   // 256-byte boundaries between the parts
     const size_t n = (size_t)N * pe;
-    const size_t eps_floats = up64(!need_eps ? 0 : h->gen ? gen_eps_floats(h->gen, N) : (size_t)N * h->w.inst->tp);
+    const size_t eps_floats = up64(!need_eps ? 0 : h->gen ? gen_eps_floats(h->gen->s, N) : (size_t)N * h->w.inst->tp);
     const size_t extra = (xt ? 0 : up64(n)) + (need_eps && !eps ? n : 0);
     float* S = nullptr;
     if (eps_floats + extra && (rc = gen_scratch(h, st, cap, eps_floats + extra, &S, "dpk_diff_loss"))) return rc;

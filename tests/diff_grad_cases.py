@@ -45,6 +45,22 @@ CASES = {
     "g16_n1": (G16_SHAPE, 1),
 }
 
+BWD_FORMS = {"dw_partial<vec>", "dw_partial<scalar>", "attention_bwd<T>", "ln_bwd", "graph_t<T>", "cheb_t", "dlg<T>",
+             "temb_bwd"}
+# hid 320 on 17 joints: a pose's [q | k | v | dO] rows (17 x 1281 floats) and the 2 hid-wide dL_g operands (2 x 17 x 641)
+# are past 64 KB of LDS, the hid-wide ones (2 x 17 x 321) are not
+BWD_FORMS_W320 = (BWD_FORMS - {"attention_bwd<T>"}) | {"attention_bwd<F>", "dlg<F>"}
+# the forms debug_grad_forms() reports; GEMM_FORMS derived by hand from gemm_choice's predicates (csrc/dpk_genplan.inc:
+# one rule for gen_forward, the training forward and the dX GEMMs) on a device of at least 200 CUs: every GEMM has at most
+# 119 rows, so 32-row tiles.  g16 (hid 32, E 128): the input ChebConv (K 15) and the output's dX (K 5) scalar, the
+# hidden GEMMs and their transposes on gemm_sk (<4> where the columns are 64 or 128), the MLP's dtp GEMM (no packed
+# copy) on gemm<32,vec>, d_k 16 on attention<TT>.  odd (hid 15, E 60): everything scalar but temb.dense.1's dX (60 x 60).
+GEMM_FORMS = {
+    "g16": {"gemm<32,scalar>", "gemm<32,vec>", "gemm_sk<2>", "gemm_sk<4>", "gemm_narrow", "attention<TT>", "graph<T>",
+            "cheb_basis<T>"},
+    "odd": {"gemm<32,scalar>", "gemm_narrow", "gemm_sk<4>", "attention<TF>", "graph<T>", "cheb_basis<T>"},
+}
+
 
 def golden_g16(load) -> dict:
     """The g16 fixture (tools/gen_goldens_grad.py) as torch tensors; gradients under "grad.<name>" """

@@ -54,7 +54,8 @@ POSE_REGIMES = ("baseline", "x10", "x1000", "zeros", "joints_equal", "bias+10_ch
 # pointer alignment.  Each row below is a model shape (hid, heads, layers, joints, edges, coords), the batch
 # sizes it runs at and, per batch size, the forms HipGCNdiff.debug_generic_forms() must report after one
 # forward (dpk_eps) under DPK_GEN_FUSED=0, on a device of at least 200 CUs (the tile-height rule then says
-# 32 rows for every GEMM here).  The sets are derived by hand from gen_forward's predicates ("The
+# 32 rows for every GEMM here).  The sets are derived by hand from the predicates of csrc/dpk_genplan.inc (gemm_choice,
+# attention_choice, graph_choice, cheb_choice: the rule gen_forward launches by; DESIGN.md, "The
 # per-op path's kernel forms"), never read off a run.  Inputs: regime("forms", shape, n=N).
 FORM_T = (0, 1, 7, 24, 49, 500, 999)          # per-pose timesteps, cycled to N
 

@@ -21,20 +21,7 @@ from diffpose_amd.schedule import make_seq, training_timesteps
 
 pytestmark = pytest.mark.gpu
 
-BWD_FORMS = {"dw_partial<vec>", "dw_partial<scalar>", "attention_bwd<T>", "ln_bwd", "graph_t<T>", "cheb_t", "dlg<T>",
-             "temb_bwd"}
-# hid 320 on 17 joints: a pose's [q | k | v | dO] rows (17 x 1281 floats) and the 2 hid-wide dL_g operands (2 x 17 x 641)
-# are past 64 KB of LDS, the hid-wide ones (2 x 17 x 321) are not
-BWD_FORMS_W320 = (BWD_FORMS - {"attention_bwd<T>"}) | {"attention_bwd<F>", "dlg<F>"}
-# derived by hand from bwd_gemm's predicates (gen_forward's) on a device of at least 200 CUs: every GEMM has at most
-# 119 rows, so 32-row tiles.  g16 (hid 32, E 128): the input ChebConv (K 15) and the output's dX (K 5) scalar, the
-# hidden GEMMs and their transposes on gemm_sk (<4> where the columns are 64 or 128), the MLP's dtp GEMM (no packed
-# copy) on gemm<32,vec>, d_k 16 on attention<TT>.  odd (hid 15, E 60): everything scalar but temb.dense.1's dX (60 x 60).
-GEMM_FORMS = {
-    "g16": {"gemm<32,scalar>", "gemm<32,vec>", "gemm_sk<2>", "gemm_sk<4>", "gemm_narrow", "attention<TT>", "graph<T>",
-            "cheb_basis<T>"},
-    "odd": {"gemm<32,scalar>", "gemm_narrow", "gemm_sk<4>", "attention<TF>", "graph<T>", "cheb_basis<T>"},
-}
+BWD_FORMS, BWD_FORMS_W320, GEMM_FORMS = GC.BWD_FORMS, GC.BWD_FORMS_W320, GC.GEMM_FORMS
 
 
 def ends_session(fn):
@@ -88,6 +75,13 @@ def models(dev):
         m.close()
 
 
+@pytest.fixture(scope="module")
+def g16(golden):
+    """(inputs, references) of the g16 fixture, computed once; do not modify"""
+    i = GC.g16_inputs(golden)
+    return i, GC.references(i)
+
+
 def _grad(m, i, dev, **kw):
     args = dict(noise_scale=i["scale"].to(dev), noise=i["e"].to(dev), mask=i["mask"].to(dev))
     args.update(kw)
@@ -112,9 +106,8 @@ def _check(tag, loss, grads, ref, scale=1.0):
 # 1. g16: the fixture's inputs
 
 @ends_session
-def test_g16_fixture(dev, golden):
-    z, i = GC.golden_g16(golden), GC.g16_inputs(golden)
-    ref = GC.references(i)
+def test_g16_fixture(dev, golden, g16):
+    z, (i, ref) = GC.golden_g16(golden), g16
     m = _model(GC.G16_SHAPE, i["sd"], dev)
     try:
         assert m.fused == 0
@@ -211,6 +204,32 @@ def test_row_partitions(dev, models, name):
     _check(f"diff_grad/{name}", loss, grads, GC.case_references(name))
     _, again = _grad(m, i, dev)
     assert torch.equal(again.flat, grads.flat)
+
+
+@ends_session
+def test_grad_honours_gemm_switches(dev, g16, monkeypatch):
+    """DPK_GEN_GEMM=lds and DPK_GEN_BM=64 reach every per-op GEMM of the gradient call (the training forward's and
+    the dX GEMMs go through the launch layer gen_forward uses), are read per call, and leave nothing behind."""
+    i, ref = g16
+    m = _model(GC.G16_SHAPE, i["sd"], dev)
+    try:
+        plain_loss, plain = _grad(m, i, dev)
+        monkeypatch.setenv("DPK_GEN_GEMM", "lds")
+        monkeypatch.setenv("DPK_GEN_BM", "64")
+        m.debug_grad_forms()
+        loss, grads = _grad(m, i, dev)
+        fwd, _ = m.debug_grad_forms()
+        assert not {f for f in fwd if f.startswith("gemm_sk<")}, fwd
+        assert {f for f in fwd if f.startswith("gemm<")} == {"gemm<64,vec>", "gemm<64,scalar>"}, fwd
+        _check("diff_grad/g16/lds64", loss, grads, ref)
+        loss2, grads2 = _grad(m, i, dev)
+        assert torch.equal(grads2.flat, grads.flat) and torch.equal(loss2, loss)
+        monkeypatch.delenv("DPK_GEN_GEMM")
+        monkeypatch.delenv("DPK_GEN_BM")
+        loss3, grads3 = _grad(m, i, dev)
+        assert torch.equal(grads3.flat, plain.flat) and torch.equal(loss3, plain_loss)
+    finally:
+        m.close()
 
 
 @ends_session
