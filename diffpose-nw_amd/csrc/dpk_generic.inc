@@ -293,6 +293,70 @@ __global__ void __launch_bounds__(256) layer_norm(const float* __restrict__ X, f
     for (int c = lane; c < D; c += 64) y[c] = ga[c] * (x[c] - mean) / (sd + 1e-6f) + gb[c];
 }
 
+// Train-mode dropout masks (DropSite, dpk_genplan.inc): counter-based, recomputed wherever they are read, never
+// stored.  One Philox call gives the four words of the elements 4 g .. 4 g + 3; element indices are 64-bit.
+__device__ __forceinline__ void drop_group(const DropSite& d, long long g, uint32_t w[4]) {
+    w[0] = (uint32_t)g;
+    w[1] = (uint32_t)((unsigned long long)g >> 32);
+    w[2] = d.dom;
+    w[3] = 0xD809u;
+    dpk::philox(w, d.k0, d.k1);
+}
+__device__ __forceinline__ bool drop_keep(const DropSite& d, const uint32_t w[4], int k) {
+    const uint32_t v = k == 0 ? w[0] : k == 1 ? w[1] : k == 2 ? w[2] : w[3];
+    return (v >> 8) >= d.thr;
+}
+// d.s where element i is kept, else 0, for a thread that walks ascending i: a new call only where i leaves the group
+struct DropRow {
+    long long g = -1;
+    uint32_t w[4];
+    __device__ __forceinline__ float factor(const DropSite& d, long long i) {
+        if ((i >> 2) != g) {
+            g = i >> 2;
+            drop_group(d, g, w);
+        }
+        return drop_keep(d, w, (int)(i & 3)) ? d.s : 0.f;
+    }
+};
+
+// o[i] = drop(x[i]) (ADD: res[i] + drop(x[i])) for the n elements from global element `base` of the site on: a kept
+// value is x d.s, a dropped one 0.  x may be o (in place).  One thread per group of four global elements, the ends
+// of the range clipped; vec (base a multiple of 4, 16-byte aligned arrays): whole groups as 16-byte accesses.
+template <bool ADD>
+__global__ void __launch_bounds__(256) drop_apply(const float* res, const float* x, float* o, long long n,
+                                                  long long base, DropSite d, int vec) {
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    const long long g = (base >> 2) + (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long lo = max(4 * g, base), hi = min(4 * g + 4, base + n);
+    if (lo >= hi) return;
+    uint32_t w[4];
+    drop_group(d, g, w);
+    if (vec && hi - lo == 4) {
+        const long long e = lo - base;
+        f32x4 v = *reinterpret_cast<const f32x4*>(x + e);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = drop_keep(d, w, k) ? v[k] * d.s : 0.f;
+        if constexpr (ADD) v = *reinterpret_cast<const f32x4*>(res + e) + v;
+        *reinterpret_cast<f32x4*>(o + e) = v;
+        return;
+    }
+    for (long long i = lo; i < hi; ++i) {
+        const float v = drop_keep(d, w, (int)(i & 3)) ? x[i - base] * d.s : 0.f;
+        if constexpr (ADD) o[i - base] = res[i - base] + v;
+        else o[i - base] = v;
+    }
+}
+// keep[i - first] = 1 or 0 for the elements first .. first + n - 1 (dpk_dropout_mask)
+__global__ void __launch_bounds__(256) drop_mask_bytes(unsigned char* __restrict__ keep, long long first, long long n,
+                                                       DropSite d) {
+    const long long g = (first >> 2) + (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long lo = max(4 * g, first), hi = min(4 * g + 4, first + n);
+    if (lo >= hi) return;
+    uint32_t w[4];
+    drop_group(d, g, w);
+    for (long long i = lo; i < hi; ++i) keep[i - first] = drop_keep(d, w, (int)(i & 3)) ? 1 : 0;
+}
+
 // Multi-head attention core (GraFormer.py:116-140): `ppb` poses per workgroup, their QKV rows
 // [q | k | v] (J x 3D floats each) staged in LDS with coalesced loads (STAGE; dynamic LDS ppb * J * RW
 // floats, used when that fits 64 KB), then one thread per (pose, head, query): scores / sqrt(dk), masked
@@ -300,10 +364,12 @@ __global__ void __launch_bounds__(256) layer_norm(const float* __restrict__ X, f
 // ascending).  VEC (dk and D multiples of 4 and 8, `out` 16-byte aligned): 16-byte LDS reads and stores, LDS row stride
 // RW = 3D + 4 (RW / 4 odd: the 16 lanes of a head reading rows q * RW hit disjoint bank quads);
 // otherwise RW = 3D + 1 (odd: distinct banks for scalar reads).
-template <bool STAGE, bool VEC>
-__global__ void __launch_bounds__(256) attention(const float* __restrict__ qkv, float* __restrict__ out, int N, int J,
-                                                 int D, int H, unsigned mask, const unsigned* __restrict__ pmask,
-                                                 int ppb) {
+// TRAIN (attention_train; the inference kernel is the body without it): dropout on the normalised probabilities
+// before P.V, element ((pose0 + p) H + h) J J + q J + j of site `drop` (drop_factor).
+template <bool STAGE, bool VEC, bool TRAIN>
+__device__ __forceinline__ void attention_body(const float* __restrict__ qkv, float* __restrict__ out, int N, int J,
+                                               int D, int H, unsigned mask, const unsigned* __restrict__ pmask,
+                                               int ppb, const DropSite& drop, long long pose0) {
     typedef float f32x4 __attribute__((ext_vector_type(4)));
     extern __shared__ __attribute__((aligned(16))) float lds_rows[];
     const int p0 = blockIdx.x * ppb, np = min(ppb, N - p0);
@@ -361,6 +427,11 @@ __global__ void __launch_bounds__(256) attention(const float* __restrict__ qkv, 
             sum += sc[j];
         }
         for (int j = 0; j < J; ++j) sc[j] = sc[j] / sum;
+        if constexpr (TRAIN) {
+            const long long i0 = (((pose0 + p) * H + h) * J + q) * J;
+            DropRow row;
+            for (int j = 0; j < J; ++j) sc[j] = sc[j] * row.factor(drop, i0 + j);
+        }
         float* o = out + ((size_t)p * J + q) * D + h * dk;
         if constexpr (VEC) {
             for (int d4 = 0; d4 < dk / 4; ++d4) {
@@ -380,6 +451,19 @@ __global__ void __launch_bounds__(256) attention(const float* __restrict__ qkv, 
             }
         }
     }
+}
+template <bool STAGE, bool VEC>
+__global__ void __launch_bounds__(256) attention(const float* __restrict__ qkv, float* __restrict__ out, int N, int J,
+                                                 int D, int H, unsigned mask, const unsigned* __restrict__ pmask,
+                                                 int ppb) {
+    attention_body<STAGE, VEC, false>(qkv, out, N, J, D, H, mask, pmask, ppb, DropSite{}, 0);
+}
+template <bool STAGE, bool VEC>
+__global__ void __launch_bounds__(256) attention_train(const float* __restrict__ qkv, float* __restrict__ out, int N,
+                                                       int J, int D, int H, unsigned mask,
+                                                       const unsigned* __restrict__ pmask, int ppb, DropSite drop,
+                                                       long long pose0) {
+    attention_body<STAGE, VEC, true>(qkv, out, N, J, D, H, mask, pmask, ppb, drop, pose0);
 }
 
 // Y[p][j][c] = sum_i Lm[j][i] X[p][i][c] (row strides ldx, ldy).  STAGE: one workgroup per pose, X_p and
@@ -859,6 +943,24 @@ struct GenOps {
         forms |= a.form;
         auto* kernel = !a.stage ? dpkg::attention<false, false> : a.vec ? dpkg::attention<true, true> : dpkg::attention<true, false>;
         hipLaunchKernelGGL(kernel, dim3(a.blocks), dim3(256), a.lds, st, qkv, out, N, s.J, s.D, s.H, mask, pmask, a.ppb);
+    }
+    // the same choice with dropout on the probabilities (the train-mode gradient call)
+    void attention_train(const float* qkv, float* out, const dpkg::DropSite& d, long long pose0) const {
+        const AttnChoice a = attention_choice(N, s.J, s.D, s.H, reinterpret_cast<uintptr_t>(out));
+        forms |= a.form;
+        auto* kernel = !a.stage ? dpkg::attention_train<false, false>
+                       : a.vec  ? dpkg::attention_train<true, true>
+                                : dpkg::attention_train<true, false>;
+        hipLaunchKernelGGL(kernel, dim3(a.blocks), dim3(256), a.lds, st, qkv, out, N, s.J, s.D, s.H, mask, pmask, a.ppb, d,
+                           pose0);
+    }
+    // o = drop(x), or res + drop(x) with res given, over n floats from global element `base` of the site
+    void drop(const float* res, const float* x, float* o, long long n, long long base, const dpkg::DropSite& d) const {
+        const auto al = [](const void* p) { return gen_al16(reinterpret_cast<uintptr_t>(p)); };
+        const int vec = (base & 3) == 0 && al(x) && al(o) && (!res || al(res));
+        const dim3 grid(gen_blocks(((base + n + 3) >> 2) - (base >> 2)));
+        if (res) hipLaunchKernelGGL(dpkg::drop_apply<true>, grid, dim3(256), 0, st, res, x, o, n, base, d, vec);
+        else hipLaunchKernelGGL(dpkg::drop_apply<false>, grid, dim3(256), 0, st, res, x, o, n, base, d, vec);
     }
     void layer_norm(const float* x, float* y, size_t ga, size_t gb) const {
         hipLaunchKernelGGL(dpkg::layer_norm, dim3((unsigned)((M() + 3) / 4)), dim3(256), 0, st, x, y, M(), s.D, W + ga, W + gb);

@@ -1,6 +1,7 @@
 // dpk_generic_bwd.inc — the gradient of the denoising objective (dpk_diff_loss_grad) on the per-op path: the
 // forward of dpk_generic.inc run once more with what the backward needs kept in the call's scratch, then the
-// backward as per-op HIP kernels, fp32 throughout, eval mode (no dropout).  Included by dpk_kernels.hip after
+// backward as per-op HIP kernels, fp32 throughout; eval mode, or train mode (dpk_diff_loss_grad_train: dropout at the
+// reference's five sites per layer, counter-based masks recomputed where they are read).  Included by dpk_kernels.hip after
 // dpk_generic.inc and dpk_grad_layout.inc; forms, grids and LDS sizes come from dpk_genplan.inc.
 //   training forward  gen_forward's ops (GenOps: the same kernels and form choices, out of place), every GEMM operand,
 //                     ReLU output and residual-stream value of every layer stored (bwd_plan: the stash)
@@ -10,6 +11,8 @@
 //                     ascending order and writes the torch layout (transposed for nn.Linear, QKV split in three)
 //   the rest          plain-VALU kernels: ln_bwd, attention_bwd, graph on L_g^T, dlg_partial + dlg_chain (to A_hat),
 //                     cheb_t, relu_bwd, joint_sum, swish_bwd, loss_grad
+//   train mode        attention_train / attention_bwd_train, drop_apply (dpk_generic.inc), relu_drop_bwd: launched
+//                     only at a site whose rate is not 0, in place of or beside the eval-mode launches (bwd_run)
 // Every sum over rows or poses is a store pass of partials over a fixed partition (DW_ROWS rows, DLG_POSES poses)
 // and an ordered sum pass: no float atomics, so the same call gives bitwise the same gradients.
 
@@ -206,9 +209,14 @@ __global__ void __launch_bounds__(256) ln_bwd(const float* __restrict__ X, const
 // dQ = dS K, dK = dS^T Q, dV = P^T dO, sums over keys / queries ascending.  Dynamic LDS 2 hb J J floats, and with
 // `stage` the pose's rows [q | k | v | dO] behind them, J rows of (4 D) | 1 floats (an odd stride: the queries of a
 // head read distinct banks); without it the rows are read from global memory (a pose too wide for 64 KB).
-__global__ void __launch_bounds__(256) attention_bwd(const float* __restrict__ qkv, const float* __restrict__ dO,
-                                                     float* __restrict__ dqkv, int J, int D, int H, unsigned mask,
-                                                     const unsigned* __restrict__ pmask, int hb, int stage) {
+// TRAIN (attention_bwd_train; the eval-mode kernel is the body without it): the forward dropped probabilities of site
+// `drop`, element ((pose0 + p) H + h) J J + q J + j, factor f = s or 0 recomputed from the counter: dP_j = (dO . V_j) f_j,
+// dS from the unmasked p as above, and P f in LDS for pass 2's dV.
+template <bool TRAIN>
+__device__ __forceinline__ void attention_bwd_body(const float* __restrict__ qkv, const float* __restrict__ dO,
+                                                   float* __restrict__ dqkv, int J, int D, int H, unsigned mask,
+                                                   const unsigned* __restrict__ pmask, int hb, int stage,
+                                                   const DropSite& drop, long long pose0) {
     extern __shared__ __attribute__((aligned(16))) float absm[];
     float* Ps = absm;
     float* Ss = absm + (size_t)hb * J * J;
@@ -257,16 +265,22 @@ __global__ void __launch_bounds__(256) attention_bwd(const float* __restrict__ q
                 sum += e;
             }
             float dot = 0.f;
+            const long long i0 = (((pose0 + p) * H + h) * J + q) * J;
+            DropRow row;
             for (int j = 0; j < J; ++j) {
                 const float pj = pr[j] / sum;
                 pr[j] = pj;
                 const float* vr = rows + j * RS + 2 * D + h * dk;
                 float dp = 0.f;
                 for (int d = 0; d < dk; ++d) dp = fmaf(go[d], vr[d], dp);
+                if constexpr (TRAIN) dp *= row.factor(drop, i0 + j);
                 sr[j] = dp;
                 dot = fmaf(pj, dp, dot);
             }
-            for (int j = 0; j < J; ++j) sr[j] = ((m >> j) & 1u) ? pr[j] * (sr[j] - dot) / sq : 0.f;
+            for (int j = 0; j < J; ++j) {
+                sr[j] = ((m >> j) & 1u) ? pr[j] * (sr[j] - dot) / sq : 0.f;
+                if constexpr (TRAIN) pr[j] *= row.factor(drop, i0 + j);
+            }
         }
         __syncthreads();
         for (int e = threadIdx.x; e < nh * J * dk; e += 256) {
@@ -286,6 +300,17 @@ __global__ void __launch_bounds__(256) attention_bwd(const float* __restrict__ q
         }
         __syncthreads();
     }
+}
+__global__ void __launch_bounds__(256) attention_bwd(const float* __restrict__ qkv, const float* __restrict__ dO,
+                                                     float* __restrict__ dqkv, int J, int D, int H, unsigned mask,
+                                                     const unsigned* __restrict__ pmask, int hb, int stage) {
+    attention_bwd_body<false>(qkv, dO, dqkv, J, D, H, mask, pmask, hb, stage, DropSite{}, 0);
+}
+__global__ void __launch_bounds__(256) attention_bwd_train(const float* __restrict__ qkv, const float* __restrict__ dO,
+                                                           float* __restrict__ dqkv, int J, int D, int H, unsigned mask,
+                                                           const unsigned* __restrict__ pmask, int hb, int stage,
+                                                           DropSite drop, long long pose0) {
+    attention_bwd_body<true>(qkv, dO, dqkv, J, D, H, mask, pmask, hb, stage, drop, pose0);
 }
 
 // P[slab][j][i] = sum over the slab's poses p (ascending) and channels c (ascending) of dY[p][j][c] X[p][i][c]:
@@ -398,6 +423,12 @@ __global__ void __launch_bounds__(256) relu_bwd(const float* __restrict__ dOut, 
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i < n) dPre[i] = R[i] > 0.f ? dOut[i] : 0.f;
 }
+// relu_bwd behind a dropout of rate p on the ReLU output (R stored dropped and scaled: R > 0 is "positive and kept")
+__global__ void __launch_bounds__(256) relu_drop_bwd(const float* __restrict__ dOut, const float* __restrict__ R,
+                                                     float* __restrict__ dPre, long long n, float s) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) dPre[i] = R[i] > 0.f ? dOut[i] * s : 0.f;
+}
 __global__ void __launch_bounds__(256) add2(const float* __restrict__ a, const float* __restrict__ b,
                                             float* __restrict__ o, long long n) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -489,9 +520,28 @@ static int bwd_prepare(dpk_handle* h) {
     return DPK_OK;
 }
 
-// dpk_diff_loss_grad once its arguments have passed: noising, the training forward, the loss, the backward
+// The dropout of one train-mode call (dpk_diff_loss_grad_train): the three rates, the seed and the global index of
+// the call's first pose.  All rates 0 (the default): dpk_diff_loss_grad's launches, every one.
+struct DropRun {
+    float sublayer = 0.f, attn = 0.f, gconv = 0.f;
+    uint64_t seed = 0;
+    long long pose0 = 0;
+    // thr = ceil(p 2^24) (the product is exact), s = 1 / (1 - p) in fp32, both taken here on the host
+    dpkg::DropSite site(int layer, int id) const {
+        const float p = id == dpkg::DROP_ATTN ? attn : id == dpkg::DROP_SUB0 || id == dpkg::DROP_SUB1 ? sublayer : gconv;
+        dpkg::DropSite d;
+        d.thr = (unsigned)ceilf(p * 16777216.0f);
+        d.s = d.thr ? 1.0f / (1.0f - p) : 1.0f;
+        d.dom = (unsigned)(layer * 8 + id);
+        d.k0 = (unsigned)seed;
+        d.k1 = (unsigned)(seed >> 32);
+        return d;
+    }
+};
+
+// dpk_diff_loss_grad(_train) once its arguments have passed: noising, the training forward, the loss, the backward
 static int bwd_run(dpk_handle* h, const float* x0, const float* t, const StartSpec& spec, uint64_t seed, float weight,
-                   float* loss, float* grads, int N, hipStream_t st) {
+                   float* loss, float* grads, int N, hipStream_t st, const DropRun& dr) {
     BwdModel* b = h->bwd;
     GenModel* g = h->gen ? h->gen : b->own;
     const Stage& s = g->s;
@@ -521,27 +571,51 @@ static int bwd_run(dpk_handle* h, const float* x0, const float* t, const StartSp
     op.temb(t, 1, N, p.tproj, &keep);
     op.cheb(p.xt, cin, p.Z0);
     op.gemm(ar, p.Z0, M, 3 * cin, s.win, W + s.bin, p.lay.empty() ? p.Hlast : p.lay[0].H, D, D, dpkg::G_BIAS);
+    // Train mode (dr): the five dropout sites of a layer fall on those seams.  p_attn is dropped inside
+    // attention_train; a sublayer's GEMM writes its branch alone (G_BIAS) and drop_apply<true> adds the residual to the
+    // dropped branch in place; a ChebConv's ReLU output is dropped in place, so R1 and R2 are stored masked and scaled.
+    // A site whose rate is 0 runs the eval-mode launches.
+    const long long MD = (long long)M * D, base = dr.pose0 * J * D;      // a [N, J, hid] site's elements of this call
     for (int l = 0; l < L; ++l) {
         const GenLayer& o = s.lay[l];
         const BwdLayerBufs& y = p.lay[l];
         float* Hnext = l + 1 < L ? p.lay[l + 1].H : p.Hlast;
+        const dpkg::DropSite att = dr.site(l, dpkg::DROP_ATTN), sub0 = dr.site(l, dpkg::DROP_SUB0),
+                             sub1 = dr.site(l, dpkg::DROP_SUB1), gc1 = dr.site(l, dpkg::DROP_GC1),
+                             gc2 = dr.site(l, dpkg::DROP_GC2);
+        if (att.thr) b->bforms |= dpkg::B_ATTN_TRAIN;
+        if (sub0.thr || sub1.thr) b->bforms |= dpkg::B_DROP_ADD;
+        if (gc1.thr || gc2.thr) b->bforms |= dpkg::B_RELU_DROP;
         op.layer_norm(y.H, y.Y0, o.n0a, o.n0b);
         op.gemm(ar, y.Y0, M, D, o.wqkv, W + o.bqkv, y.QKV, 3 * D, 3 * D, dpkg::G_BIAS);
-        op.attention(y.QKV, y.A);
-        HIPCHK(h, copy(y.H1, y.H, (size_t)M * D));
-        op.gemm(ar, y.A, M, D, o.wo, W + o.bo, y.H1, D, D, dpkg::G_RESID);
+        if (att.thr) op.attention_train(y.QKV, y.A, att, dr.pose0);
+        else op.attention(y.QKV, y.A);
+        if (sub0.thr) {
+            op.gemm(ar, y.A, M, D, o.wo, W + o.bo, y.H1, D, D, dpkg::G_BIAS);
+            op.drop(y.H, y.H1, y.H1, MD, base, sub0);
+        } else {
+            HIPCHK(h, copy(y.H1, y.H, (size_t)M * D));
+            op.gemm(ar, y.A, M, D, o.wo, W + o.bo, y.H1, D, D, dpkg::G_RESID);
+        }
         op.layer_norm(y.H1, y.Y1, o.n1a, o.n1b);
         op.graph(W + o.lg, y.Y1, D, y.G1);
         op.gemm(ar, y.G1, M, D, o.w1, W + o.b1, y.F, 2 * D, 2 * D, dpkg::G_RELU);
         op.graph(W + o.lg, y.F, 2 * D, y.G2);
-        HIPCHK(h, copy(y.H2, y.H1, (size_t)M * D));
-        op.gemm(ar, y.G2, M, 2 * D, o.w2, W + o.b2, y.H2, D, D, dpkg::G_RESID);
+        if (sub1.thr) {
+            op.gemm(ar, y.G2, M, 2 * D, o.w2, W + o.b2, y.H2, D, D, dpkg::G_BIAS);
+            op.drop(y.H1, y.H2, y.H2, MD, base, sub1);
+        } else {
+            HIPCHK(h, copy(y.H2, y.H1, (size_t)M * D));
+            op.gemm(ar, y.G2, M, 2 * D, o.w2, W + o.b2, y.H2, D, D, dpkg::G_RESID);
+        }
         op.cheb(y.H2, D, y.Z1);
         op.gemm(ar, y.Z1, M, 3 * D, o.wc1, W + o.bc1, y.R1, D, D, dpkg::G_RELU);
+        if (gc1.thr) op.drop(nullptr, y.R1, y.R1, MD, base, gc1);
         hipLaunchKernelGGL(dpkg::add_temb, blocks((long long)M * D), dim3(256), 0, st, y.R1, p.tproj + (size_t)l * D, L * D,
                            p.C1, (long long)M * D, D, J);
         op.cheb(p.C1, D, y.Z2);
         op.gemm(ar, y.Z2, M, 3 * D, o.wc2, W + o.bc2, y.R2, D, D, dpkg::G_RELU);
+        if (gc2.thr) op.drop(nullptr, y.R2, y.R2, MD, base, gc2);
         hipLaunchKernelGGL(dpkg::add2, blocks((long long)M * D), dim3(256), 0, st, y.H2, y.R2, Hnext, (long long)M * D);
     }
     op.cheb(p.Hlast, D, p.Zout);
@@ -583,6 +657,11 @@ static int bwd_run(dpk_handle* h, const float* x0, const float* t, const StartSp
     auto relu_bwd = [&](const float* dOut, const float* R, float* dPre, long long n) {
         hipLaunchKernelGGL(dpkg::relu_bwd, blocks(n), dim3(256), 0, st, dOut, R, dPre, n);
     };
+    // behind a ChebConv's dropout (R stored dropped and scaled), or relu_bwd where the site is off
+    auto relu_drop_bwd = [&](const float* dOut, const float* R, float* dPre, const dpkg::DropSite& d) {
+        if (!d.thr) return relu_bwd(dOut, R, dPre, MD);
+        hipLaunchKernelGGL(dpkg::relu_drop_bwd, blocks(MD), dim3(256), 0, st, dOut, R, dPre, MD, d.s);
+    };
     auto ln_bwd = [&](const float* X, const float* dY, size_t ga, size_t da, size_t db) {
         b->bforms |= dpkg::B_LN_BWD;
         hipLaunchKernelGGL(dpkg::ln_bwd, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, X, dY, W + ga, p.dH, p.tD1, M, D);
@@ -596,7 +675,6 @@ static int bwd_run(dpk_handle* h, const float* x0, const float* t, const StartSp
         auto* kernel = c.stage ? dpkg::dlg_partial<true> : dpkg::dlg_partial<false>;
         hipLaunchKernelGGL(kernel, dim3(c.blocks), dim3(256), c.lds, st, dY, X, P, N, J, C);
     };
-    const long long MD = (long long)M * D;
 
     hipLaunchKernelGGL(dpkg::loss_grad, blocks((long long)M * cout), dim3(256), 0, st, p.eps, (long long)M * cout, pe,
                        spec.scale, spec.rows, spec.noise, (unsigned long long)seed, weight, p.dEps);
@@ -607,21 +685,26 @@ static int bwd_run(dpk_handle* h, const float* x0, const float* t, const StartSp
         const GenLayer& o = s.lay[l];
         const BwdLayerBufs& y = p.lay[l];
         const GradLayer& q = gl.lay[l];
-        // H3 = H2 + relu(Z2 Wc2 + bc2)
-        relu_bwd(p.dH, y.R2, p.tD1, MD);
+        const dpkg::DropSite att = dr.site(l, dpkg::DROP_ATTN), sub0 = dr.site(l, dpkg::DROP_SUB0),
+                             sub1 = dr.site(l, dpkg::DROP_SUB1);
+        // H3 = H2 + drop(relu(Z2 Wc2 + bc2))
+        relu_drop_bwd(p.dH, y.R2, p.tD1, dr.site(l, dpkg::DROP_GC2));
         dW(y.Z2, 3 * D, M, 3 * D, p.tD1, D, D, false, D, one(q.c2w, q.c2b));
         dX(p.tD1, M, D, o.wc2, 3 * D, p.t3D);
         cheb_t(p.t3D, p.tD2, false);                 // dC1
         // C1 = relu(Z1 Wc1 + bc1) + temb_proj_l
         hipLaunchKernelGGL(dpkg::joint_sum, blocks((long long)N * D), dim3(256), 0, st, p.tD2, p.dtp + (size_t)l * D, L * D, N,
                            J, D);
-        relu_bwd(p.tD2, y.R1, p.tD1, MD);
+        relu_drop_bwd(p.tD2, y.R1, p.tD1, dr.site(l, dpkg::DROP_GC1));
         dW(y.Z1, 3 * D, M, 3 * D, p.tD1, D, D, false, D, one(q.c1w, q.c1b));
         dX(p.tD1, M, D, o.wc1, 3 * D, p.t3D);
         cheb_t(p.t3D, p.dH, true);                   // dH2
         // H2 = H1 + (L_g relu((L_g Y1) W1 + b1)) W2 + b2
-        dW(y.G2, 2 * D, M, 2 * D, p.dH, D, D, true, D, one(q.f2w, q.f2b));
-        dX(p.dH, M, D, o.w2, 2 * D, p.t2Da);         // dG2
+        // (train mode: the branch's gradient is drop(dH2), into tD1, free here; the residual path keeps dH)
+        const float* dB1 = p.dH;
+        if (sub1.thr) op.drop(nullptr, p.dH, p.tD1, MD, base, sub1), dB1 = p.tD1;
+        dW(y.G2, 2 * D, M, 2 * D, dB1, D, D, true, D, one(q.f2w, q.f2b));
+        dX(dB1, M, D, o.w2, 2 * D, p.t2Da);          // dG2
         dlg(p.t2Da, y.F, 2 * D, p.Plg + (size_t)lgslabs * J * J);
         op.graph(WT + o.lg, p.t2Da, 2 * D, p.t2Db, &b->bforms);    // dF
         relu_bwd(p.t2Db, y.F, p.t2Da, 2 * MD);
@@ -633,13 +716,20 @@ static int bwd_run(dpk_handle* h, const float* x0, const float* t, const StartSp
                            WT + b->arena.ahat + (size_t)l * b->arena.jj4, grads + q.ahat, J);
         ln_bwd(y.H1, p.tD2, o.n1a, q.n1a, q.n1b);
         // H1 = H + attention(LN0(H)) Wo + bo
-        dW(y.A, D, M, D, p.dH, D, D, true, D, one(q.lw[3], q.lb[3]));
-        dX(p.dH, M, D, o.wo, D, p.tD1);              // dA
+        // (train mode: drop(dH1) into tD2, free after ln_bwd)
+        const float* dB0 = p.dH;
+        if (sub0.thr) op.drop(nullptr, p.dH, p.tD2, MD, base, sub0), dB0 = p.tD2;
+        dW(y.A, D, M, D, dB0, D, D, true, D, one(q.lw[3], q.lb[3]));
+        dX(dB0, M, D, o.wo, D, p.tD1);               // dA
         {
             const AttnBwdChoice a = attention_bwd_choice(J, D, s.H);
             b->bforms |= a.stage ? dpkg::B_ATTN_BWD_STAGED : dpkg::B_ATTN_BWD_GLOBAL;
-            hipLaunchKernelGGL(dpkg::attention_bwd, dim3((unsigned)N), dim3(256), a.lds, st, y.QKV, p.tD1, p.t3D, J, D, s.H,
-                               h->mask, h->pmask, a.hb, a.stage ? 1 : 0);
+            if (att.thr)
+                hipLaunchKernelGGL(dpkg::attention_bwd_train, dim3((unsigned)N), dim3(256), a.lds, st, y.QKV, p.tD1, p.t3D, J,
+                                   D, s.H, h->mask, h->pmask, a.hb, a.stage ? 1 : 0, att, dr.pose0);
+            else
+                hipLaunchKernelGGL(dpkg::attention_bwd, dim3((unsigned)N), dim3(256), a.lds, st, y.QKV, p.tD1, p.t3D, J, D,
+                                   s.H, h->mask, h->pmask, a.hb, a.stage ? 1 : 0);
         }
         dW(y.Y0, D, M, D, p.t3D, 3 * D, 3 * D, true, D,
            dpkg::DwDst{{grads + q.lw[0], grads + q.lw[1], grads + q.lw[2]}, {grads + q.lb[0], grads + q.lb[1], grads + q.lb[2]}});

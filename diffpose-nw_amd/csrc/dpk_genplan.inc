@@ -47,7 +47,22 @@ enum BwdForm : unsigned {
     B_TEMB_BWD = 1u << 8,
     B_ATTN_BWD_GLOBAL = 1u << 9,
     B_DLG_GLOBAL = 1u << 10,
+    B_ATTN_TRAIN = 1u << 11,      // attention_train / attention_bwd_train: a nonzero rate on p_attn
+    B_DROP_ADD = 1u << 12,        // drop_apply<true>: a nonzero rate on the sublayers' outputs
+    B_RELU_DROP = 1u << 13,       // drop_apply<false> on a ChebConv's ReLU output: a nonzero rate there
 };
+
+// One dropout site of a train-mode gradient call (dpk_diff_loss_grad_train): element i of the site's tensor (its flat
+// index over the whole batch) keeps its value, times s, iff word i & 3 of Philox4x32-10 at counter
+// {i >> 2 lo, i >> 2 hi, dom, 0xD809} under the key {k0, k1}, shifted right by 8, is at least thr.  thr 0: the site is
+// off (the eval-mode launches run in its place).
+struct DropSite {
+    unsigned thr = 0;
+    float s = 1.0f;
+    unsigned dom = 0;             // layer * 8 + site
+    unsigned k0 = 0, k1 = 0;      // drop_seed's two halves
+};
+enum DropSiteId { DROP_ATTN = 0, DROP_SUB0 = 1, DROP_SUB1 = 2, DROP_GC1 = 3, DROP_GC2 = 4, DROP_SITES = 5 };
 
 }  // namespace dpkg
 

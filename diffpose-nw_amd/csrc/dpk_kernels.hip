@@ -889,7 +889,7 @@ static int enter_call(dpk_handle* h, int N, const char* who, hipStream_t st, boo
 
 extern "C" {
 
-int dpk_version(void) { return 102; }
+int dpk_version(void) { return 103; }
 
 int dpk_kernel_geometry(int* ppw, int* tpw, int* lds) {
     if (ppw) *ppw = P;
@@ -1365,30 +1365,79 @@ int dpk_diff_loss(dpk_handle* h, const float* x0, const float* t, const float* s
     return sched_note_use(h, sc, st, cap);
 }
 
-int dpk_diff_loss_grad(dpk_handle* h, const float* x0, const float* t, const float* scale, int scale_rows,
-                       const float* noise, uint64_t seed, float weight, float* loss, float* grads, int N, void* stream) {
-    if (!h) return DPK_E_INVALID;
-    if (N < 0 || (N > 0 && (!x0 || !t || !grads))) return fail(h, DPK_E_INVALID, "dpk_diff_loss_grad: bad args");
+// dpk_diff_loss_grad and dpk_diff_loss_grad_train behind their own argument checks (`who` names the entry point)
+static int grad_call(dpk_handle* h, const std::string& who, const float* x0, const float* t, const float* scale,
+                     int scale_rows, const float* noise, uint64_t seed, float weight, float* loss, float* grads, int N,
+                     void* stream, const DropRun& dr) {
     if (h->kind != 0)
-        return fail(h, DPK_E_UNSUPPORTED, "dpk_diff_loss_grad: GCNpose handle (coords 2->3) has no diffusion objective");
+        return fail(h, DPK_E_UNSUPPORTED, who + ": GCNpose handle (coords 2->3) has no diffusion objective");
     if (h->gemm_mode != 0)
-        return fail(h, DPK_E_UNSUPPORTED, "dpk_diff_loss_grad: the backward is fp32 (per-op kernels on the fp32 MFMA); "
-                                          "set gemm mode 0 (fp32) for the call");
-    int rc = noising_check(h, "dpk_diff_loss_grad", N, scale, scale_rows);
+        return fail(h, DPK_E_UNSUPPORTED, who + ": the backward is fp32 (per-op kernels on the fp32 MFMA); "
+                                                "set gemm mode 0 (fp32) for the call");
+    int rc = noising_check(h, who.c_str(), N, scale, scale_rows);
     if (rc) return rc;
     if ((rc = check_ready(h))) return rc;
     if (N == 0) return DPK_OK;
     hipStream_t st = (hipStream_t)stream;
     bool cap = false;
-    if ((rc = enter_call(h, N, "dpk_diff_loss_grad", st, &cap))) return rc;
+    if ((rc = enter_call(h, N, who.c_str(), st, &cap))) return rc;
     if (cap)
-        return fail(h, DPK_E_STATE, "dpk_diff_loss_grad: not callable while a graph is being captured (its scratch and "
-                                    "its arenas are allocated by the call)");
+        return fail(h, DPK_E_STATE, who + ": not callable while a graph is being captured (its scratch and "
+                                          "its arenas are allocated by the call)");
     sched_sweep(h);
     if ((rc = bwd_prepare(h))) return rc;
     const StartSpec spec{0.f, 0.f, scale, scale ? scale_rows : 1, noise};
-    if ((rc = bwd_run(h, x0, t, spec, seed, weight, loss, grads, N, st))) return rc;
+    if ((rc = bwd_run(h, x0, t, spec, seed, weight, loss, grads, N, st, dr))) return rc;
     return sched_note_use(h, h->sched, st, false);
+}
+
+int dpk_diff_loss_grad(dpk_handle* h, const float* x0, const float* t, const float* scale, int scale_rows,
+                       const float* noise, uint64_t seed, float weight, float* loss, float* grads, int N, void* stream) {
+    if (!h) return DPK_E_INVALID;
+    if (N < 0 || (N > 0 && (!x0 || !t || !grads))) return fail(h, DPK_E_INVALID, "dpk_diff_loss_grad: bad args");
+    return grad_call(h, "dpk_diff_loss_grad", x0, t, scale, scale_rows, noise, seed, weight, loss, grads, N, stream,
+                     DropRun{});
+}
+
+// a dropout rate must lie in [0, 1): the text of the refusal, empty when it does
+static std::string drop_rate_error(const char* name, float p) {
+    if (p >= 0.f && p < 1.f) return "";
+    return std::string("dropout rate ") + name + " = " + std::to_string(p) + " is not in [0, 1)";
+}
+
+int dpk_diff_loss_grad_train(dpk_handle* h, const float* x0, const float* t, const float* scale, int scale_rows,
+                             const float* noise, uint64_t seed, float weight, const dpk_dropout* drop,
+                             uint64_t drop_seed, int64_t pose0, float* loss, float* grads, int N, void* stream) {
+    if (!h) return DPK_E_INVALID;
+    const std::string who = "dpk_diff_loss_grad_train";
+    if (N < 0 || (N > 0 && (!x0 || !t || !grads))) return fail(h, DPK_E_INVALID, who + ": bad args");
+    if (!drop) return fail(h, DPK_E_INVALID, who + ": drop is NULL");
+    const std::pair<const char*, float> rates[3] = {{"sublayer", drop->sublayer}, {"attn", drop->attn}, {"gconv", drop->gconv}};
+    for (const auto& r : rates) {
+        const std::string e = drop_rate_error(r.first, r.second);
+        if (!e.empty()) return fail(h, DPK_E_INVALID, who + ": " + e);
+    }
+    if (pose0 < 0) return fail(h, DPK_E_INVALID, who + ": pose0 = " + std::to_string(pose0) + " is negative");
+    DropRun dr;
+    dr.sublayer = drop->sublayer, dr.attn = drop->attn, dr.gconv = drop->gconv;
+    dr.seed = drop_seed, dr.pose0 = pose0;
+    return grad_call(h, who, x0, t, scale, scale_rows, noise, seed, weight, loss, grads, N, stream, dr);
+}
+
+int dpk_dropout_mask(uint64_t drop_seed, int layer, int site, float p, int64_t first, int64_t n, uint8_t* keep,
+                     void* stream) {
+    if (layer < 0 || site < 0 || site >= dpkg::DROP_SITES || !(p >= 0.f && p < 1.f) || first < 0 || n < 0 ||
+        (n > 0 && !keep))
+        return DPK_E_INVALID;
+    if (n == 0) return DPK_OK;
+    DropRun dr;
+    dr.sublayer = dr.attn = dr.gconv = p;
+    dr.seed = drop_seed;
+    const dpkg::DropSite d = dr.site(layer, site);
+    const long long groups = ((first + n + 3) >> 2) - (first >> 2);
+    hipLaunchKernelGGL(dpkg::drop_mask_bytes, dim3(gen_blocks(groups)), dim3(256), 0, (hipStream_t)stream, keep,
+                       (long long)first, (long long)n, d);
+    return hipGetLastError() == hipSuccess ? DPK_OK : DPK_E_HIP;
 }
 
 int dpk_param_count(const dpk_handle* h) {

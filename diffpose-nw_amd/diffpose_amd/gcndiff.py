@@ -78,6 +78,8 @@ class _HipModel:
         self.hid_dim = hid
         self.n_head = nh
         self.coords_dim = tuple(coords)
+        # config.model.dropout: only a train-mode gradient call reads it (diffusion_loss_grad(dropout=True))
+        self.dropout = float(getattr(getattr(config, "model", None), "dropout", 0.0) or 0.0)
         adj = adj.detach().cpu().numpy() if torch.is_tensor(adj) else np.asarray(adj)
         self.adj = np.ascontiguousarray(adj, dtype=np.float32)
         if self.adj.shape != (npts, npts):
@@ -111,9 +113,10 @@ class _HipModel:
 
     def train(self, mode: bool = True):
         if mode:
-            raise NotImplementedError(f"{type(self).__name__} has no train mode (no dropout on the device): take "
-                                      "gradient steps in eval mode with HipGCNdiff.diffusion_loss_grad or "
-                                      "runner.Diffpose.train_step (SURVEY §8f f4)")
+            raise NotImplementedError(f"{type(self).__name__} has no train mode (forward, sample and diffusion_loss "
+                                      "run without dropout on the device): take gradient steps with "
+                                      "HipGCNdiff.diffusion_loss_grad (dropout= for the reference's train-mode "
+                                      "masks) or runner.Diffpose.train_step (SURVEY §8f f4)")
         return self.eval()
 
     def to(self, *a, **k):
@@ -268,7 +271,8 @@ class _HipModel:
 
     # bit i of dpk_debug_grad_forms' second word (csrc/dpk_generic_bwd.inc, dpkg::BwdForm)
     GRAD_FORMS = ("dw_partial<vec>", "dw_partial<scalar>", "attention_bwd<T>", "ln_bwd", "graph_t<T>", "graph_t<F>",
-                  "cheb_t", "dlg<T>", "temb_bwd", "attention_bwd<F>", "dlg<F>")
+                  "cheb_t", "dlg<T>", "temb_bwd", "attention_bwd<F>", "dlg<F>", "attention<train>", "drop_add",
+                  "relu_drop")
 
     def debug_grad_forms(self):
         """Test hook (dpk_debug_grad_forms): (GENERIC_FORMS names of the training forward's and the dX GEMMs'
@@ -515,13 +519,46 @@ class HipGCNdiff(_HipModel):
             out.append((name.value.decode(), int(off.value), int(num.value)))
         return out, (out[-1][1] + out[-1][2] if out else 0)
 
-    def diffusion_loss_grad(self, x0, t, betas, noise_scale=None, noise=None, seed: int = 0, mask=None, weight=None):
+    DROP_SITES = ("attn", "sub0", "sub1", "gc1", "gc2")      # site ids 0..4 of the dropout masks
+
+    def dropout_rates(self, dropout):
+        """``diffusion_loss_grad``'s ``dropout`` as (sublayer, attn, gconv): ``True`` is the reference's
+        ``(config.model.dropout, 0.1, 0.1)`` (models/gcndiff.py:79-85), a 3-tuple explicit rates"""
+        if dropout is True:
+            return (float(self.dropout), 0.1, 0.1)
+        rates = tuple(float(v) for v in dropout)
+        if len(rates) != 3:
+            raise ValueError(f"dropout must be None, True or (sublayer, attn, gconv), got {dropout!r}")
+        return rates
+
+    def dropout_mask(self, layer: int, site, p: float, seed: int, n: int, first: int = 0):
+        """``dpk_dropout_mask``: the uint8 keep mask (1 kept, 0 dropped) of elements ``first .. first + n - 1`` of
+        ``(layer, site)`` under ``seed`` at rate ``p``; ``site`` an id 0..4 or a name of ``DROP_SITES``.  Element i is
+        the flat index in the site's tensor over the whole batch ([N, heads, J, J] for attn, else [N, J, hid])."""
+        site = self.DROP_SITES.index(site) if isinstance(site, str) else int(site)
+        keep = torch.empty(int(n), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            rc = _lib.lib().dpk_dropout_mask(ctypes.c_uint64(seed & (2**64 - 1)), int(layer), site, ctypes.c_float(p),
+                                             int(first), int(n), keep.data_ptr() if n else None, stream)
+        if rc:
+            raise _lib.DpkError("dpk_dropout_mask", rc, f"layer {layer} site {site} p {p} first {first} n {n}")
+        return keep
+
+    def diffusion_loss_grad(self, x0, t, betas, noise_scale=None, noise=None, seed: int = 0, mask=None, weight=None,
+                            dropout=None, dropout_seed: int = 0, pose0: int = 0):
         """``diffusion_loss`` and its gradient: ``(loss [N], grads)`` with ``grads`` an OrderedDict name -> view of one
         flat device tensor (``grads.flat``), every parameter of the state_dict under its name and with the reference's
         shape: d(sum_n weight * loss[n]) / d parameter, what ``loss_diff.backward()`` leaves in ``p.grad``
         (runners/diffpose_frame.py:226-229) for the default ``weight`` = 1 / N.  Eval mode (dropout off), fp32, the
         per-op kernels on every handle; the same arguments give bitwise the same gradients.  Arguments and their
-        checks as in ``diffusion_loss``; a rank holding a shard of a batch of B poses passes ``weight=1 / B``."""
+        checks as in ``diffusion_loss``; a rank holding a shard of a batch of B poses passes ``weight=1 / B``.
+
+        ``dropout`` (None: the call above) asks for the train-mode gradient, ``dpk_diff_loss_grad_train``: ``True`` for
+        the reference's rates ``(config.model.dropout, 0.1, 0.1)`` or a tuple (sublayer, attn, gconv), with
+        counter-based masks under ``dropout_seed`` (include/diffpose_kernels.h has the rule, ``dropout_mask`` the
+        masks); ``loss`` is then the train-mode loss.  ``pose0``: the global index of this shard's first pose, so that
+        the shards of a batch draw the batch's masks."""
         from collections import OrderedDict
 
         from .weights import param_shapes
@@ -542,12 +579,17 @@ class HipGCNdiff(_HipModel):
         loss = torch.empty(n, dtype=torch.float32, device=self.device)
         flat = torch.zeros(total, dtype=torch.float32, device=self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        rc = _lib.lib().dpk_diff_loss_grad(self._h, x0.data_ptr(), tt.data_ptr(),
-                                           sc.data_ptr() if sc is not None else None, rows,
-                                           e.data_ptr() if e is not None else None,
-                                           ctypes.c_uint64(seed & (2**64 - 1)), ctypes.c_float(weight),
-                                           loss.data_ptr(), flat.data_ptr(), n, stream)
-        _lib.check(self._h, "dpk_diff_loss_grad", rc)
+        head = (self._h, x0.data_ptr(), tt.data_ptr(), sc.data_ptr() if sc is not None else None, rows,
+                e.data_ptr() if e is not None else None, ctypes.c_uint64(seed & (2**64 - 1)), ctypes.c_float(weight))
+        tail = (loss.data_ptr(), flat.data_ptr(), n, stream)
+        if dropout is None:
+            rc = _lib.lib().dpk_diff_loss_grad(*head, *tail)
+            _lib.check(self._h, "dpk_diff_loss_grad", rc)
+        else:
+            rates = _lib.DpkDropout(*self.dropout_rates(dropout))
+            rc = _lib.lib().dpk_diff_loss_grad_train(*head, ctypes.byref(rates),
+                                                     ctypes.c_uint64(dropout_seed & (2**64 - 1)), int(pose0), *tail)
+            _lib.check(self._h, "dpk_diff_loss_grad_train", rc)
         shapes = param_shapes(hid=self.hid_dim, n_layers=self.num_layer, n_pts=self.n_pts, coords=self.coords_dim)
 
         class _Grads(OrderedDict):

@@ -392,14 +392,20 @@ class Diffpose:
         ``config.optim.grad_clip`` when the config has one (:229), calls ``optimizer.step()`` (:230) and loads the
         updated ``params`` back into the handle.  Returns ``loss_diff`` (a float, :226).
 
-        The reference trains with dropout ``config.model.dropout``; the device has no dropout masks, so a config whose
-        dropout is not 0 raises NotImplementedError unless ``args.train_without_dropout`` is set."""
+        The reference trains with dropout ``config.model.dropout`` (:195 ``model_diff.train()``).  With
+        ``args.train_dropout`` set the step is the reference's train-mode step: the gradient call runs with dropout at
+        the reference's rates (``diffusion_loss_grad(dropout=True)``) under counter-based masks whose seed is one
+        63-bit ``torch.randint`` from ``generator``, drawn after ``e`` and ``t``, so the same generator gives the same
+        ``e`` and ``t`` with or without the flag.  Without it a config whose dropout is not 0 raises
+        NotImplementedError unless ``args.train_without_dropout`` is set (eval-mode gradients)."""
         from .schedule import training_timesteps
 
         p_drop = float(getattr(self.config.model, "dropout", 0.0) or 0.0)
-        if p_drop != 0.0 and not getattr(self.args, "train_without_dropout", False):
-            raise NotImplementedError(f"config.model.dropout = {p_drop}: the device backward runs without dropout masks; "
-                                      "set args.train_without_dropout to train in eval mode, or dropout to 0")
+        train_dropout = bool(getattr(self.args, "train_dropout", False))
+        if p_drop != 0.0 and not train_dropout and not getattr(self.args, "train_without_dropout", False):
+            raise NotImplementedError(f"config.model.dropout = {p_drop}: the device backward runs without dropout masks "
+                                      "by default; set args.train_dropout to train with dropout as the reference does, "
+                                      "args.train_without_dropout to train in eval mode, or dropout to 0")
         x0 = torch.as_tensor(targets_uvxyz).detach().to(torch.float32)
         noise_scale = torch.as_tensor(noise_scale).detach().to(torch.float32)
         B = x0.shape[0]
@@ -409,8 +415,11 @@ class Diffpose:
         e = torch.randn((B, self.n_pts, 5), generator=generator)                   # :214
         t = training_timesteps(B, self.num_timesteps, generator=generator)        # :216-218
         dev = lambda a: a.to(self.device)   # noqa: E731
+        drop = {}
+        if train_dropout:
+            drop = dict(dropout=True, dropout_seed=int(torch.randint(0, 2 ** 63 - 1, (1,), generator=generator)))
         loss, grads = self.model_diff.diffusion_loss_grad(dev(x0), t, self.betas, noise_scale=dev(noise_scale),
-                                                          noise=dev(e), mask=self.src_mask)
+                                                          noise=dev(e), mask=self.src_mask, **drop)
         for name, g in grads.items():
             params[name].grad = g.to(params[name].dtype)
         clip = getattr(getattr(self.config, "optim", None), "grad_clip", None)

@@ -258,6 +258,44 @@ int dpk_diff_loss(dpk_handle* h, const float* x0_dev, const float* t_dev, const 
 int dpk_diff_loss_grad(dpk_handle* h, const float* x0_dev, const float* t_dev, const float* scale_dev, int scale_rows,
                        const float* noise_dev, uint64_t seed, float weight, float* loss_dev, float* grads_dev, int N,
                        void* stream);
+/* The same gradient in train mode: dropout at the reference's five sites per layer l, with counter-based masks.
+ *   site   id  module of the reference                      tensor the mask covers   rate
+ *   attn   0   atten_layers.l.self_attn.dropout (p_attn)    [N, n_head, n_pts, n_pts] drop->attn (reference 0.1)
+ *   sub0   1   atten_layers.l.sublayer.0.dropout            [N, n_pts, hid]           drop->sublayer (config.model.dropout)
+ *   sub1   2   atten_layers.l.sublayer.1.dropout            [N, n_pts, hid]           drop->sublayer
+ *   gc1    3   gconv_layers.l.gconv1.dropout (on the relu)  [N, n_pts, hid]           drop->gconv (reference 0.1)
+ *   gc2    4   gconv_layers.l.gconv2.dropout                [N, n_pts, hid]           drop->gconv
+ * The mask (this formula is the contract).  Element i is its flat index in the tensor above over the whole batch: for a
+ * call whose first pose is global pose `pose0`, i = (pose0 + n) * per_pose + local, per_pose = n_pts * hid, or
+ * n_head * n_pts * n_pts for attn.  Element i of (l, site) under drop_seed keeps its value iff (w >> 8) >= thr, with
+ *   w    output word i & 3 of Philox4x32-10 at counter {(i >> 2) lo, (i >> 2) hi, l * 8 + site, 0xD809},
+ *        key {drop_seed lo, drop_seed hi} (one call serves four consecutive elements),
+ *   thr  (uint32) ceilf(p * 16777216.0f), taken once on the host (the product is exact, the decision an integer
+ *        comparison).
+ * A kept element becomes x * s, s = 1.0f / (1.0f - p) in fp32 taken on the host; a dropped one 0.0f.  Rate 0 keeps
+ * everything and multiplies by nothing.  Counter word 3 (0xD809) is not the normal draws' (0x5EED): the masks are
+ * disjoint from e and from eta's draws under an equal seed.  Forward and backward each recompute the decision from the
+ * counter; no mask is stored, the call's scratch is dpk_diff_loss_grad's.
+ *   drop, drop_seed  the rates and the masks' key
+ *   pose0            the global index of the call's first pose: the shards of one batch, each with weight 1 / B, add up
+ *                    to the unsharded gradient.  pose0 keys the masks only: it does not move the counter-based e of a
+ *                    NULL noise_dev, which stays normal_noise(seed, -1, element of this call).
+ *   loss_dev         the train-mode loss per pose
+ * Everything else is dpk_diff_loss_grad's: the arguments, the layout of grads_dev, the caller-memory contract (N = 0
+ * touches nothing), bitwise repeatability, its refusals.  With all three rates 0 the outputs are bitwise
+ * dpk_diff_loss_grad's (the same launches).  DPK_E_INVALID, with the offending value in dpk_last_error, for a NULL
+ * drop, a rate that is negative, NaN or >= 1, or pose0 < 0. */
+typedef struct { float sublayer, attn, gconv; } dpk_dropout;
+int dpk_diff_loss_grad_train(dpk_handle* h, const float* x0_dev, const float* t_dev, const float* scale_dev,
+                             int scale_rows, const float* noise_dev, uint64_t seed, float weight,
+                             const dpk_dropout* drop, uint64_t drop_seed, int64_t pose0, float* loss_dev,
+                             float* grads_dev, int N, void* stream);
+/* The mask itself, without a handle (to replay a step elsewhere): keep_dev[i - first] = 1 or 0 for elements
+ * first .. first + n - 1 of (layer, site) under drop_seed at rate p; exactly n bytes written on `stream` of the
+ * current device, n = 0 touches nothing.  DPK_E_INVALID for a negative layer, a site outside 0..4, a rate outside
+ * [0, 1), negative first or n, or a NULL keep_dev with n > 0. */
+int dpk_dropout_mask(uint64_t drop_seed, int layer, int site, float p, int64_t first, int64_t n, uint8_t* keep_dev,
+                     void* stream);
 /* Parameters of a GCNdiff handle (0 for NULL or a GCNpose handle), and entry i of their layout in grads_dev. */
 int dpk_param_count(const dpk_handle* h);
 int dpk_param_layout(const dpk_handle* h, int i, const char** name, int64_t* offset, int64_t* numel);
@@ -447,11 +485,12 @@ int dpk_profile_read(dpk_handle* h, float* ms_out, int cap, int* count);
 int dpk_debug_split(dpk_handle* h, int mode, int* fallbacks);
 int dpk_debug_resources(dpk_handle* h, int* out, int n);
 int dpk_debug_generic_forms(dpk_handle* h, unsigned* forms);
-/* dpk_debug_grad_forms: the same for dpk_diff_loss_grad, then cleared: *gemm_forms the dpk_debug_generic_forms bits of
+/* dpk_debug_grad_forms: the same for dpk_diff_loss_grad(_train), then cleared: *gemm_forms the dpk_debug_generic_forms bits of
  * its training forward and of its dX GEMMs, *bwd_forms the backward's own (bit 0 dw_partial with 16-byte loads, 1 with
  * scalar loads, 2 attention_bwd with the pose's rows staged in LDS, 3 ln_bwd, 4..5 graph on L_g^T staged / unstaged,
  * 6 cheb_t, 7 dlg_partial staged (+ dlg_chain), 8 the timestep MLP's backward, 9 attention_bwd unstaged, 10 dlg_partial
- * unstaged). */
+ * unstaged; of a train-mode call, each only where its site's rate is not 0: 11 attention with dropout on the
+ * probabilities, forward and backward, 12 the sublayers' drop + residual add, 13 the dropout on a ChebConv's ReLU). */
 int dpk_debug_grad_forms(dpk_handle* h, unsigned* gemm_forms, unsigned* bwd_forms);
 int dpk_debug_sampler_kernels(dpk_handle* h, uint32_t* ids, int cap, int* count);
 
