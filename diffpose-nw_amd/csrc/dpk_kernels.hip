@@ -329,6 +329,7 @@ struct InstWeights {
 
 struct GenModel;   // dpk_generic.inc: the per-op forward for model shapes no instance is compiled for
 struct BwdModel;   // dpk_generic_bwd.inc: what dpk_diff_loss_grad keeps (built on its first call)
+struct TrainState; // dpk_train.inc: the device-side optimiser's arrays, between dpk_train_begin and dpk_train_end
 struct dpk_handle {
     int device = 0;
     GenModel* gen = nullptr;       // non-null: this handle's shape runs on the per-op path (then w.inst is null)
@@ -356,6 +357,7 @@ struct dpk_handle {
     Stage stage;                   // host staging of the weights and the graph, whatever the shape
     uint64_t stage_serial = 0;     // bumped whenever the staging is uploaded anew (pack_upload)
     BwdModel* bwd = nullptr;       // dpk_diff_loss_grad's arenas (and, on a sampler instance, its per-op model)
+    TrainState* train = nullptr;   // non-null: training (dpk_train_begin); the device holds the weights, the staging lags
     int gemm_mode = 0;             // 0: fp32 MFMA, 1: 3x fp16-split MFMA, 2: bf16 MFMA (dpk_set_gemm_mode)
     int tile_waves = 0;            // dpk_set_tile_waves: 4 or 8 waves on the 4-pose tiles of dpk_sample; 0 the mode's default
     bool have_graph = false, have_weights = false;
@@ -801,6 +803,8 @@ static SampleArgs pose_args(const dpk_handle* h, const float* arena, const float
 #include "dpk_generic.inc"
 #include "dpk_grad_layout.inc"
 #include "dpk_generic_bwd.inc"
+#include "dpk_train_layout.inc"
+#include "dpk_train.inc"
 
 // ---------------------------------------------------------------------------------------
 // The compiled sampler instances: which shapes have a fused kernel, on which tile, with which kernel modes.
@@ -889,7 +893,7 @@ static int enter_call(dpk_handle* h, int N, const char* who, hipStream_t st, boo
 
 extern "C" {
 
-int dpk_version(void) { return 103; }
+int dpk_version(void) { return 104; }
 
 int dpk_kernel_geometry(int* ppw, int* tpw, int* lds) {
     if (ppw) *ppw = P;
@@ -983,6 +987,7 @@ void dpk_destroy(dpk_handle* h) {
     if (h->flags) (void)hipFree(h->flags);
     gen_free(h->gen);
     bwd_free(h->bwd);
+    train_free(h->train);
     // hipFree waits for the device, so in-flight launches finish before their buffers go
     if (h->sched) sched_free(h->sched);
     for (Sched* s : h->retired) sched_free(s);
@@ -1016,6 +1021,8 @@ static int pack_upload(dpk_handle* h) {
 
 int dpk_set_graph(dpk_handle* h, const float* adj) {
     if (!h || !adj) return fail(h, DPK_E_INVALID, "dpk_set_graph: null argument");
+    if (h->train) return fail(h, DPK_E_STATE, "dpk_set_graph: not while training (the upload would overwrite the device's weights "
+                                              "from a stale staging); dpk_train_end first");
     stage_set_graph(h->stage, adj);
     h->have_graph = true;
     return h->have_weights ? pack_upload(h) : DPK_OK;
@@ -1043,6 +1050,8 @@ int dpk_load_weights(dpk_handle* h, const char* const* names, const float* const
     if (!h || !names || !ptrs || !numels || n <= 0) return fail(h, DPK_E_INVALID, "dpk_load_weights: bad args");
     for (int i = 0; i < n; ++i)
         if (!names[i] || !ptrs[i]) return fail(h, DPK_E_INVALID, "dpk_load_weights: null entry");
+    if (h->train) return fail(h, DPK_E_STATE, "dpk_load_weights: not while training (dpk_train_set writes the parameters of a "
+                                              "run); dpk_train_end first");
     std::string err;
     if (!stage_load(h->stage, names, ptrs, numels, n, err))
         return fail(h, DPK_E_WEIGHTS, "dpk_load_weights: " + err);
@@ -1187,6 +1196,7 @@ int dpk_eps(dpk_handle* h, const float* x, const float* t, float* eps, int N, vo
     if (N < 0 || (N > 0 && (!x || !t || !eps))) return fail(h, DPK_E_INVALID, "dpk_eps: bad args");
     int rc = check_ready(h);
     if (rc) return rc;
+    if ((rc = train_fresh(h, "dpk_eps"))) return rc;
     if (N == 0) return DPK_OK;
     hipStream_t st = (hipStream_t)stream;
     bool cap = false;
@@ -1237,6 +1247,7 @@ int dpk_sample_start(dpk_handle* h, const float* x, float* out, float* xs, float
     if (N < 0 || (N > 0 && (!x || !out))) return fail(h, DPK_E_INVALID, "dpk_sample: bad args");
     int rc = check_ready(h);
     if (rc) return rc;
+    if ((rc = train_fresh(h, "dpk_sample"))) return rc;
     const bool start_on = t_start >= 0;
     StartSpec start{};
     if (start_on && (rc = start_spec(h, "dpk_sample_start", N, t_start, scale, scale_rows, start_noise, &start))) return rc;
@@ -1312,6 +1323,7 @@ int dpk_diff_loss(dpk_handle* h, const float* x0, const float* t, const float* s
     if (rc) return rc;
     const bool need_eps = loss || eps;          // x_t alone needs neither weights nor a graph, like dpk_q_sample
     if (need_eps && (rc = check_ready(h))) return rc;
+    if (need_eps && (rc = train_fresh(h, "dpk_diff_loss"))) return rc;
     if (N == 0) return DPK_OK;
     Sched* sc = h->sched;
     hipStream_t st = (hipStream_t)stream;
@@ -1463,6 +1475,89 @@ int dpk_param_layout(const dpk_handle* h, int i, const char** name, int64_t* off
     if (name) *name = g->e[i].name.c_str();
     if (offset) *offset = g->e[i].offset;
     if (numel) *numel = g->e[i].numel;
+    return DPK_OK;
+}
+
+int dpk_train_begin(dpk_handle* h, const dpk_optim_config* cfg) {
+    if (!h) return DPK_E_INVALID;
+    HIPCHK(h, hipSetDevice(h->device));
+    return train_begin(h, cfg);
+}
+
+int dpk_train_apply(dpk_handle* h, const float* grads, float lr, float* gnorm, void* stream) {
+    if (!h) return DPK_E_INVALID;
+    if (!h->train) return fail(h, DPK_E_STATE, "dpk_train_apply: training has not begun (dpk_train_begin)");
+    if (!grads) return fail(h, DPK_E_INVALID, "dpk_train_apply: grads_dev is NULL");
+    if (!(lr >= 0.f)) return fail(h, DPK_E_INVALID, "dpk_train_apply: lr = " + std::to_string(lr) + " is negative or NaN");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    bool cap = false;
+    const int rc = capturing(h, st, &cap);
+    if (rc) return rc;
+    if (cap) return fail(h, DPK_E_STATE, "dpk_train_apply: not callable while a graph is being captured (the step count and "
+                                         "Adam's bias corrections are the host's, by value)");
+    return train_apply(h, grads, lr, gnorm, st);
+}
+
+int dpk_train_sync(dpk_handle* h) {
+    if (!h) return DPK_E_INVALID;
+    if (!h->train) return fail(h, DPK_E_STATE, "dpk_train_sync: training has not begun (dpk_train_begin)");
+    return train_sync(h);
+}
+
+// `which` of dpk_train_get / dpk_train_set as the array, or null with the refusal's text in h
+static float* train_array(dpk_handle* h, const char* who, int which) {
+    static const char* const NAMES[5] = {"params", "exp_avg", "exp_avg_sq", "max_exp_avg_sq", "the EMA shadow"};
+    if (!h->train) return fail(h, DPK_E_STATE, std::string(who) + ": training has not begun (dpk_train_begin)"), nullptr;
+    if (which < 0 || which > 4)
+        return fail(h, DPK_E_INVALID, std::string(who) + ": which = " + std::to_string(which) + " is not in 0..4"), nullptr;
+    if (!h->train->arr[which])
+        return fail(h, DPK_E_INVALID, std::string(who) + ": which = " + std::to_string(which) + " (" + NAMES[which] +
+                                          ") is not kept: dpk_train_begin was called without " +
+                                          (which == 3 ? "amsgrad" : "an ema_mu >= 0")), nullptr;
+    return h->train->arr[which];
+}
+
+int dpk_train_get(dpk_handle* h, int which, float* out, int64_t* step, void* stream) {
+    if (!h) return DPK_E_INVALID;
+    float* a = train_array(h, "dpk_train_get", which);
+    if (!a) return h->train ? DPK_E_INVALID : DPK_E_STATE;
+    if (!out) return fail(h, DPK_E_INVALID, "dpk_train_get: out_dev is NULL");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipMemcpyAsync(out, a, h->train->F * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (step) *step = h->train->step;
+    return DPK_OK;
+}
+
+int dpk_train_set(dpk_handle* h, int which, const float* in, int64_t step, void* stream) {
+    if (!h) return DPK_E_INVALID;
+    float* a = train_array(h, "dpk_train_set", which);
+    if (!a) return h->train ? DPK_E_INVALID : DPK_E_STATE;
+    if (!in) return fail(h, DPK_E_INVALID, "dpk_train_set: in_dev is NULL");
+    if (step < -1) return fail(h, DPK_E_INVALID, "dpk_train_set: step = " + std::to_string(step) + " (-1 leaves the count alone)");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    bool cap = false;
+    const int rc = capturing(h, st, &cap);
+    if (rc) return rc;
+    if (cap) return fail(h, DPK_E_STATE, "dpk_train_set: not callable while a graph is being captured");
+    HIPCHK(h, hipMemcpyAsync(a, in, h->train->F * 4, hipMemcpyDeviceToDevice, st));
+    if (step >= 0) h->train->step = step;
+    if (which == 0) {
+        train_refresh_launch(h, st);
+        HIPCHK(h, hipGetLastError());
+        h->train->host_stale = true;
+    }
+    return DPK_OK;
+}
+
+int dpk_train_end(dpk_handle* h) {
+    if (!h) return DPK_E_INVALID;
+    if (!h->train) return fail(h, DPK_E_STATE, "dpk_train_end: training has not begun (dpk_train_begin)");
+    const int rc = train_sync(h);
+    if (rc) return rc;
+    train_free(h->train);
+    h->train = nullptr;
     return DPK_OK;
 }
 

@@ -18,7 +18,8 @@ ERRORS = {-1: "DPK_E_INVALID", -2: "DPK_E_UNSUPPORTED", -3: "DPK_E_HIP", -4: "DP
 # every symbol include/diffpose_kernels.h declares
 EXPORTS = ("dpk_version", "dpk_create", "dpk_set_graph", "dpk_load_weights", "dpk_set_mask", "dpk_set_pose_masks",
            "dpk_set_schedule", "dpk_eps", "dpk_sample", "dpk_sample_noise", "dpk_sample_start", "dpk_q_sample", "dpk_diff_loss", "dpk_diff_loss_grad", "dpk_diff_loss_grad_train", "dpk_dropout_mask",
-           "dpk_param_count", "dpk_param_layout", "dpk_ddim_update", "dpk_ddim_update_noise",
+           "dpk_param_count", "dpk_param_layout", "dpk_train_begin", "dpk_train_apply", "dpk_train_sync", "dpk_train_get",
+           "dpk_train_set", "dpk_train_end", "dpk_ddim_update", "dpk_ddim_update_noise",
            "dpk_pose", "dpk_pose_metrics", "dpk_pose_metrics_n", "dpk_gmm_sample", "dpk_gmm_sample_f64", "dpk_gmm_sample_n",
            "dpk_gmm_sample_f64_n", "dpk_set_gemm_mode", "dpk_gemm_modes", "dpk_fused",
            "dpk_set_tail_plan", "dpk_set_tile_waves", "dpk_debug_split", "dpk_debug_resources", "dpk_debug_generic_forms", "dpk_debug_grad_forms", "dpk_debug_sampler_kernels",
@@ -35,6 +36,12 @@ class DpkConfig(ctypes.Structure):
 class DpkDropout(ctypes.Structure):
     """dpk_dropout: the rates of a train-mode gradient call (the reference: config.model.dropout, 0.1, 0.1)"""
     _fields_ = [("sublayer", ctypes.c_float), ("attn", ctypes.c_float), ("gconv", ctypes.c_float)]
+
+
+class DpkOptimConfig(ctypes.Structure):
+    """dpk_optim_config: torch.optim.Adam's constants, the clip and the EMA rate of a device-side training run"""
+    _fields_ = [("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float), ("amsgrad", ctypes.c_int),
+                ("grad_clip", ctypes.c_float), ("ema_mu", ctypes.c_float)]
 
 
 class DpkError(RuntimeError):
@@ -89,6 +96,12 @@ def lib() -> ctypes.CDLL:
     L.dpk_dropout_mask.argtypes = [u64, i32, i32, ctypes.c_float, i64, i64, vp, vp]
     L.dpk_param_count.argtypes = [vp]
     L.dpk_param_layout.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(i64), ctypes.POINTER(i64)]
+    L.dpk_train_begin.argtypes = [vp, ctypes.POINTER(DpkOptimConfig)]
+    L.dpk_train_apply.argtypes = [vp, vp, ctypes.c_float, vp, vp]
+    L.dpk_train_sync.argtypes = [vp]
+    L.dpk_train_get.argtypes = [vp, i32, vp, ctypes.POINTER(i64), vp]
+    L.dpk_train_set.argtypes = [vp, i32, vp, i64, vp]
+    L.dpk_train_end.argtypes = [vp]
     L.dpk_debug_grad_forms.argtypes = [vp, ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint)]
     L.dpk_ddim_update.argtypes = [vp, vp, vp, vp, vp, i64, i32, u64, vp]
     L.dpk_ddim_update_noise.argtypes = [vp, vp, vp, vp, vp, i64, i32, u64, vp, vp]

@@ -90,11 +90,15 @@ class _HipModel:
         self._pose_bits = None       # per-pose key masks (device int32 words), kept alive while bound
         self._mask_hold = []         # per-pose mask arrays a captured graph reads (kept until close)
         self._sched_key = None
+        self._trainer = None         # an open DeviceAdam (diffpose_amd/optim.py): the device holds the weights
         self.training = False
 
     # -- nn.Module-like surface -------------------------------------------------------
     def load_state_dict(self, state_dict, strict: bool = True):
         """Accept the reference's states[0] (with/without 'module.'), torch tensors or numpy."""
+        if getattr(self, "_trainer", None) is not None:
+            raise RuntimeError("load_state_dict while a DeviceAdam is open on this model: the device holds the weights of "
+                               "the run (DeviceAdam.load_params writes them; close() ends the run)")
         sd = normalize_state_dict(state_dict, kind=self.KIND, n_layers=self.num_layer, hid=self.hid_dim,
                                   n_pts=self.n_pts, coords=self.coords_dim)
         names = list(sd.keys())
@@ -106,6 +110,24 @@ class _HipModel:
         _lib.check(self._h, "dpk_load_weights", L.dpk_load_weights(self._h, c_names, c_ptrs, c_num, len(arrs)))
         self._state = sd
         return self
+
+    def state_dict(self):
+        """name -> tensor of the loaded weights; while a ``DeviceAdam`` is open on the model, the parameters on the
+        device (a fresh copy, on the model's device)."""
+        from collections import OrderedDict
+
+        tr = getattr(self, "_trainer", None)
+        if tr is not None:
+            return tr.params_state_dict()
+        return OrderedDict((k, torch.from_numpy(np.array(v, dtype=np.float32))) for k, v in self._state.items())
+
+    def _train_sync(self) -> None:
+        """Before a sampler-path call: while a ``DeviceAdam`` is open on a persistent-sampler model and a step has run
+        since the last sync, ``dpk_train_sync`` (a device-wide wait and a host repack); never under a capture, where the
+        call itself then refuses with the reason."""
+        tr = getattr(self, "_trainer", None)
+        if tr is not None and tr._stale and self.fused and not torch.cuda.is_current_stream_capturing():
+            tr.sync()
 
     def eval(self):
         self.training = False
@@ -305,6 +327,9 @@ class _HipModel:
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None
+        tr, self._trainer = getattr(self, "_trainer", None), None
+        if tr is not None:
+            tr._open = False         # dpk_destroy frees the trainer's arrays
         if h:
             _lib.lib().dpk_destroy(h)
         self._mask_hold = []
@@ -349,6 +374,7 @@ class HipGCNdiff(_HipModel):
         self._sync_mask(mask)
         self._check_mask_batch(n)
         self._note_mask_use()
+        self._train_sync()
         eps = torch.empty_like(x)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         L = _lib.lib()
@@ -405,6 +431,7 @@ class HipGCNdiff(_HipModel):
         n = x.shape[0]
         self._check_mask_batch(n)
         self._note_mask_use()
+        self._train_sync()
         out = torch.empty_like(x) if out is None else out
         xs = x0s = None
         if trajectory:
@@ -495,6 +522,7 @@ class HipGCNdiff(_HipModel):
         self._sync_mask(mask)
         self._check_mask_batch(n)
         self._note_mask_use()
+        self._train_sync()
         loss = torch.empty(n, dtype=torch.float32, device=self.device)
         xt = torch.empty_like(x0) if return_parts else None
         eps = torch.empty_like(x0) if return_parts else None
@@ -600,6 +628,38 @@ class HipGCNdiff(_HipModel):
             grads[name] = flat[off:off + num].view(shapes[name])
         grads.flat = flat
         return loss, grads
+
+    def device_optimizer(self, config=None, *, lr=None, betas=(0.9, 0.999), eps: float = 1e-8, amsgrad: bool = False,
+                         grad_clip=None, ema_rate=None):
+        """A ``DeviceAdam`` (diffpose_amd/optim.py) on this model: the parameters move to the device for the run, and
+        ``optimizer.step(grads)`` is clip + Adam + EMA + the refresh of the weights in a few launches.  With ``config``
+        (the reference's): ``config.optim.{lr, eps, amsgrad, grad_clip}`` (the betas are the reference's
+        fixed (0.9, 0.999), common/utils.py:41-43), ``config.model.ema_rate`` when ``config.model.ema`` is set; keyword arguments given
+        explicitly win.  RMSProp and SGD stay on the torch path (``runner.Diffpose.train_step`` with a torch
+        optimiser)."""
+        from .optim import DeviceAdam
+
+        if config is not None:
+            o = config.optim
+            name = getattr(o, "optimizer", "Adam")
+            if name != "Adam":
+                raise NotImplementedError(f"config.optim.optimizer = {name!r}: the device-side optimiser is Adam; train "
+                                          "with a torch optimiser through runner.Diffpose.train_step(..., params=...)")
+            if getattr(o, "weight_decay", 0):
+                raise NotImplementedError(f"config.optim.weight_decay = {o.weight_decay}: the device-side Adam has none; "
+                                          "use the torch path")
+            lr = o.lr if lr is None else lr
+            eps = getattr(o, "eps", eps)
+            amsgrad = getattr(o, "amsgrad", amsgrad)
+            grad_clip = getattr(o, "grad_clip", None) if grad_clip is None else grad_clip
+            m = getattr(config, "model", None)
+            if ema_rate is None and getattr(m, "ema", False):
+                ema_rate = m.ema_rate
+        if lr is None:
+            raise TypeError("device_optimizer needs lr= (or a config with optim.lr)")
+        if getattr(self, "_trainer", None) is not None:
+            raise RuntimeError("a DeviceAdam is already open on this model")
+        return DeviceAdam(self, lr=lr, betas=betas, eps=eps, amsgrad=amsgrad, grad_clip=grad_clip, ema_rate=ema_rate)
 
     def ddim_update(self, xt, et, step: int, seed: int = 0, want_x0: bool = True, noise=None):
         """x_{t-1} (and x0) from an external eps for schedule step ``step``; ``noise``: this step's

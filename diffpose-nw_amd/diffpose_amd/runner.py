@@ -383,7 +383,7 @@ class Diffpose:
         self.epoch_loss_diff = epoch.avg
         return epoch.avg
 
-    def train_step(self, targets_uvxyz, noise_scale, optimizer, params, generator=None):
+    def train_step(self, targets_uvxyz, noise_scale, optimizer, params=None, generator=None, return_losses: bool = False):
         """One gradient step on one batch: the body of the reference's training loop (runners/diffpose_frame.py:211-233)
         with the model in eval mode (dropout off).  Draws ``e`` (:214) and the antithetic ``t`` (:216-218) as
         ``diffusion_loss`` does (torch's default generator, or ``generator``), takes the per-pose losses and every
@@ -397,7 +397,12 @@ class Diffpose:
         the reference's rates (``diffusion_loss_grad(dropout=True)``) under counter-based masks whose seed is one
         63-bit ``torch.randint`` from ``generator``, drawn after ``e`` and ``t``, so the same generator gives the same
         ``e`` and ``t`` with or without the flag.  Without it a config whose dropout is not 0 raises
-        NotImplementedError unless ``args.train_without_dropout`` is set (eval-mode gradients)."""
+        NotImplementedError unless ``args.train_without_dropout`` is set (eval-mode gradients).
+
+        With a ``DeviceAdam`` (``model_diff.device_optimizer(config)``) as ``optimizer`` the step stays on the device: the
+        gradient call, then ``optimizer.step(grads)`` (clip, Adam, EMA and the refresh of the weights the kernels read);
+        no ``.grad`` assignments, no ``load_state_dict``, ``params`` unused.  ``return_losses`` returns the per-pose
+        losses (float32 [B] on the device) instead of their mean as a float, which costs a wait for the device."""
         from .schedule import training_timesteps
 
         p_drop = float(getattr(self.config.model, "dropout", 0.0) or 0.0)
@@ -420,6 +425,13 @@ class Diffpose:
             drop = dict(dropout=True, dropout_seed=int(torch.randint(0, 2 ** 63 - 1, (1,), generator=generator)))
         loss, grads = self.model_diff.diffusion_loss_grad(dev(x0), t, self.betas, noise_scale=dev(noise_scale),
                                                           noise=dev(e), mask=self.src_mask, **drop)
+        from .optim import DeviceAdam
+
+        if isinstance(optimizer, DeviceAdam):
+            optimizer.step(grads)
+            return loss if return_losses else float(loss.mean())
+        if params is None:
+            raise TypeError("train_step with a torch optimiser needs params (name -> torch parameter)")
         for name, g in grads.items():
             params[name].grad = g.to(params[name].dtype)
         clip = getattr(getattr(self.config, "optim", None), "grad_clip", None)
@@ -427,7 +439,28 @@ class Diffpose:
             torch.nn.utils.clip_grad_norm_(list(params.values()), clip)
         optimizer.step()
         self.model_diff.load_state_dict({k: v.detach() for k, v in params.items()})
-        return float(loss.mean())
+        return loss if return_losses else float(loss.mean())
+
+    def train_epoch(self, batches, optimizer, generator=None):
+        """The inner loop of the reference's training epoch (runners/diffpose_frame.py:203-236) over ``batches`` of
+        ``(targets_uvxyz [B,n_pts,5], noise_scale [B,n_pts,5], ...)`` with a ``DeviceAdam``: one ``train_step`` per
+        batch.  Every step's per-pose losses stay on the device and are read once, after the last step, so the loop
+        itself never waits for the device; returns the epoch's ``AverageMeter`` value (:233, ``update(loss_diff, B)``),
+        also kept as ``epoch_loss_diff``."""
+        from .optim import DeviceAdam
+
+        if not isinstance(optimizer, DeviceAdam):
+            raise TypeError("train_epoch runs the device-side step: pass model_diff.device_optimizer(...); a torch "
+                            "optimiser takes train_step(..., params=...) per batch")
+        kept = []
+        for batch in batches:
+            losses = self.train_step(batch[0], batch[1], optimizer, generator=generator, return_losses=True)
+            kept.append(losses)
+        epoch = metrics.AverageMeter()
+        for losses in kept:
+            epoch.update(float(losses.cpu().mean()), losses.numel())
+        self.epoch_loss_diff = epoch.avg
+        return epoch.avg
 
     def log_performance_metrics(self, output_path=None):
         """Summary of the per-batch inference times and peak-memory deltas collected under

@@ -300,6 +300,83 @@ int dpk_dropout_mask(uint64_t drop_seed, int layer, int site, float p, int64_t f
 int dpk_param_count(const dpk_handle* h);
 int dpk_param_layout(const dpk_handle* h, int i, const char** name, int64_t* offset, int64_t* numel);
 
+/* The optimiser step on the device: clip_grad_norm_, Adam and the EMA of the reference's loop body
+ * (runners/diffpose_frame.py:229-236) on parameters that stay on the device for a training run.  Every array below is
+ * flat fp32 in grads_dev's layout (dpk_param_layout), F floats = the last entry's offset + numel.
+ *   beta1, beta2, eps, amsgrad   torch.optim.Adam's (the reference: 0.9, 0.999, config.optim.eps, config.optim.amsgrad)
+ *   grad_clip                    config.optim.grad_clip; <= 0: no clipping (the norm is still computed and reported)
+ *   ema_mu                       config.model.ema_rate; < 0: no EMA shadow
+ * beta1, beta2 and ema_mu are read as the decimals they were written as: the shortest decimal that rounds to the float
+ * passed (0.999f is 0.999), in double.  1 - beta2 from the float itself would be off by 1.3e-5 of its value, and with it
+ * every exp_avg_sq.
+ *
+ * dpk_train_begin (a configuration call: it waits for the device) needs a GCNdiff handle with weights and a graph.  It
+ * allocates params (from the loaded weights, back in their torch layouts; A_hat as loaded), exp_avg and exp_avg_sq
+ * (zero), max_exp_avg_sq (zero, with amsgrad) and the EMA shadow (a copy of params, with ema_mu >= 0), sets the step
+ * count to 0, and builds what dpk_diff_loss_grad's first call builds (a persistent-sampler handle's per-op model, the
+ * transposed weights).  DPK_E_UNSUPPORTED on a GCNpose handle; DPK_E_STATE without weights or a graph, or when already
+ * begun; DPK_E_INVALID, the offending value in dpk_last_error, for a NULL cfg, a beta outside [0, 1), eps < 0 or NaN,
+ * ema_mu > 1 or NaN.
+ *
+ * dpk_train_apply is one step: four launches on `stream`, no host wait, no allocation.  grads_dev (exactly F floats,
+ * read only; what dpk_diff_loss_grad(_train) wrote, all-reduced by the caller where there are several ranks) and
+ * gnorm_dev (one float, or NULL) follow the caller-memory contract above.  In order, every operation one fp32 rounding
+ * unless it says fp64, nothing fused but the two fmaf of step 3 (this order is the contract):
+ *   1. norm.  The squares of all F floats are summed in fp64 (each square exact) over a fixed partition: part b of 256
+ *      holds elements [b c, (b + 1) c), c = ceil(F / 256); thread t of 256 adds its elements t, t + 256, ... of the part
+ *      in ascending order; the 256 threads' sums, then the 256 parts' sums, are added in a binary tree (x[i] += x[i + w],
+ *      w = 128, 64, .. 1).  gnorm = (float) sqrt(sum), the root in fp64.  No atomics: the same input gives the same bits.
+ *   2. clip.  coef = fminf(grad_clip / (gnorm + 1e-6f), 1.0f), a NaN quotient staying NaN (torch's clamp); 1.0f with
+ *      grad_clip <= 0.  It stays on the device.  g = grads_dev[i] * coef; a non-finite norm propagates as in
+ *      clip_grad_norm_(error_if_nonfinite=False).
+ *   3. Adam, weight_decay 0, at step k = count + 1.  The host takes, in double and each rounded once to fp32:
+ *      omb1 = 1 - beta1, omb2 = 1 - beta2, step_size = lr / (1 - beta1^k), bc2_sqrt = sqrt(1 - beta2^k).  Per element:
+ *        m = fmaf(g - m, omb1, m)                     (the difference rounded, then one rounding over product + sum)
+ *        v = fmaf(omb2 * g, g, v * beta2)             (omb2 * g and v * beta2 rounded, then one rounding)
+ *        vmax = v > vmax or v is NaN ? v : vmax;  used = vmax          (amsgrad; otherwise used = v)
+ *        p = p - (step_size * m) / (sqrtf(used) / bc2_sqrt + eps)
+ *      (torch's single-tensor path: lerp_, mul_ + addcmul_, maximum, addcdiv_, with the two fusions torch's CPU kernels
+ *      make in lerp_ and addcmul_; division and square root correctly rounded).
+ *   4. EMA (with a shadow): shadow = a * p + b * shadow, a = (float)(1.0 - mu), b = (float)mu, two products and a sum:
+ *      EMAHelper.update's (1. - mu) * p + mu * shadow on fp32 tensors.
+ *   5. refresh.  Everything the per-op forward and backward read is rewritten from params, on the device: the forward's
+ *      weight arena and its gemm_sk copies, the transposed arena and its copies, the A_hat rows, and each layer's
+ *      GraphNet Laplacian and its transpose, computed in the weight load's order (column sums ascending in fp32,
+ *      1.0f / sqrtf(r + 1e-5f), (d_i a_ij) d_j).  The result is bitwise what dpk_load_weights of the same parameters
+ *      builds (csrc/dpk_train_layout.inc, checked on the CPU).  The Chebyshev terms do not depend on the parameters.
+ * The padding between entries carries zero gradients and stays zero (with eps = 0 it becomes 0 / 0).
+ * On a per-op handle every later call on `stream` (dpk_eps, dpk_sample, dpk_diff_loss, the gradient calls, recorded
+ * K-step loops) reads the new weights.  On a persistent-sampler handle the gradient calls do too (they run the per-op
+ * model), but the sampler's own arenas and the host staging are not rewritten per step: dpk_sample*, dpk_eps and
+ * dpk_diff_loss return DPK_E_STATE, naming dpk_train_sync, from an apply until dpk_train_sync has run.  Calls in flight
+ * on other streams that read the weights are the caller's to order against the step.
+ * DPK_E_STATE when training has not begun or `stream` is capturing; DPK_E_INVALID for a NULL grads_dev or a negative
+ * or NaN lr.
+ *
+ * dpk_train_sync (a configuration call: it waits for the device) downloads params, refills the host staging and, on a
+ * persistent-sampler handle, repacks and uploads the sampler's arenas (recomputing the schedules' timestep
+ * projections).  The per-op arenas stay as the refresh left them.
+ * dpk_train_end syncs and frees the trainer's arrays: the handle is an ordinary one with the trained weights.  While
+ * training, dpk_load_weights and dpk_set_graph return DPK_E_STATE; dpk_destroy frees everything.
+ *
+ * dpk_train_get / dpk_train_set copy exactly F floats between device memory and one array on `stream`, for
+ * checkpoints: which = 0 params, 1 exp_avg, 2 exp_avg_sq, 3 max_exp_avg_sq, 4 the EMA shadow (3 without amsgrad, 4
+ * without a shadow, or a value outside 0..4: DPK_E_INVALID).  get: *step (may be NULL) receives the step count.  set:
+ * step >= 0 sets the count, -1 leaves it; setting params runs the refresh (and a persistent-sampler handle needs a
+ * sync again); DPK_E_STATE on a capturing stream. */
+typedef struct {
+    float beta1, beta2, eps;
+    int   amsgrad;
+    float grad_clip;
+    float ema_mu;
+} dpk_optim_config;
+int dpk_train_begin(dpk_handle* h, const dpk_optim_config* cfg);
+int dpk_train_apply(dpk_handle* h, const float* grads_dev, float lr, float* gnorm_dev, void* stream);
+int dpk_train_sync(dpk_handle* h);
+int dpk_train_get(dpk_handle* h, int which, float* out_dev, int64_t* step, void* stream);
+int dpk_train_set(dpk_handle* h, int which, const float* in_dev, int64_t step, void* stream);
+int dpk_train_end(dpk_handle* h);
+
 /* One DDIM update for an externally computed eps (generic model callables):
  * the per-element body of common/utils_diff.py:59-65 for schedule step `step`
  * (0 = first executed step, t = seq[K-1]).  x0_dev may be NULL; xnext_dev may be xt_dev. */
