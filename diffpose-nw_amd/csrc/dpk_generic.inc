@@ -357,6 +357,31 @@ __global__ void __launch_bounds__(256) drop_mask_bytes(unsigned char* __restrict
     for (long long i = lo; i < hi; ++i) keep[i - first] = drop_keep(d, w, (int)(i & 3)) ? 1 : 0;
 }
 
+// The draws of one training step for poses pose0 .. pose0 + n - 1 of a batch of `batch` poses (dpk_train_draws), each a
+// function of its seed and the global index alone.  Work item i < ne = n * pe is element i of e (global element
+// pose0 * pe + i, the draw qsample_at takes for a NULL noise at pose0 = 0); item ne + k is the timestep of pose
+// pose0 + k: the reference's antithetic pair cat([r, T - 1 - r])[:batch] with h = batch / 2 + 1 draws r, r the top 32
+// bits of counter_word(t_seed, q) scaled to 0 .. T - 1 in integers (T <= 2^24: the product fits 64 bits, the float is
+// exact).  ne or n is 0 for an output the caller does not ask for.  Plain 4-byte stores: the caller's arrays are 4-byte
+// aligned and no more.
+__global__ void __launch_bounds__(256) train_draws(float* __restrict__ e, float* __restrict__ t, long long ne, long long n,
+                                                   long long e0, long long pose0, long long batch, int T,
+                                                   unsigned long long e_seed, unsigned long long t_seed) {
+    const long long stride = (long long)gridDim.x * 256;
+    const long long end = ne + n;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < end; i += stride) {
+        if (i < ne) {
+            e[i] = dpk::normal_noise(e_seed, -1, e0 + i);
+            continue;
+        }
+        const long long p = pose0 + (i - ne), h = batch / 2 + 1;
+        const bool first = p < h;
+        const unsigned long long w = dpk_counter::counter_word(t_seed, (unsigned long long)(first ? p : p - h));
+        const long long r = (long long)(((w >> 32) * (unsigned long long)T) >> 32);
+        t[i - ne] = (float)(first ? r : (long long)T - 1 - r);
+    }
+}
+
 // Multi-head attention core (GraFormer.py:116-140): `ppb` poses per workgroup, their QKV rows
 // [q | k | v] (J x 3D floats each) staged in LDS with coalesced loads (STAGE; dynamic LDS ppb * J * RW
 // floats, used when that fits 64 KB), then one thread per (pose, head, query): scores / sqrt(dk), masked

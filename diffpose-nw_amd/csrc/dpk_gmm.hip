@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "diffpose_kernels.h"
+#include "dpk_counter.inc"
 
 namespace dpk_gmm {
 
@@ -25,11 +26,7 @@ constexpr int KMAX = 64;   // components per joint accepted by the kernel
 
 // uniform double in [0, 1) with 53 random bits from a counter (seeded mode; not numpy's stream)
 __device__ __forceinline__ double counter_uniform(uint64_t seed, uint64_t ctr) {
-    uint64_t z = seed + 0x9E3779B97F4A7C15ull * (ctr + 1);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (double)(z >> 11) * (1.0 / 9007199254740992.0);
+    return (double)(dpk_counter::counter_word(seed, ctr) >> 11) * (1.0 / 9007199254740992.0);
 }
 
 // T: the dtype of the caller's arrays (float32, or float64 as numpy would hold them).  The choice

@@ -146,6 +146,7 @@ static thread_local uint32_t last_kernel = KERNEL_NONE;
 #include "dpk_stage.inc"
 #include "dpk_genplan.inc"
 #include "dpk_scratch.inc"
+#include "dpk_counter.inc"
 
 // All the host knows a compiled sampler instance by: its shape half (dpk_stage.inc) and how to launch it.  One
 // per instance namespace, built where the table is (INSTANCES).
@@ -893,7 +894,7 @@ static int enter_call(dpk_handle* h, int N, const char* who, hipStream_t st, boo
 
 extern "C" {
 
-int dpk_version(void) { return 104; }
+int dpk_version(void) { return 105; }
 
 int dpk_kernel_geometry(int* ppw, int* tpw, int* lds) {
     if (ppw) *ppw = P;
@@ -1449,6 +1450,21 @@ int dpk_dropout_mask(uint64_t drop_seed, int layer, int site, float p, int64_t f
     const long long groups = ((first + n + 3) >> 2) - (first >> 2);
     hipLaunchKernelGGL(dpkg::drop_mask_bytes, dim3(gen_blocks(groups)), dim3(256), 0, (hipStream_t)stream, keep,
                        (long long)first, (long long)n, d);
+    return hipGetLastError() == hipSuccess ? DPK_OK : DPK_E_HIP;
+}
+
+int dpk_train_draws(uint64_t e_seed, uint64_t t_seed, int T, int64_t batch, int64_t pose0, int n, int pose_floats,
+                    float* e, float* t, void* stream) {
+    if (T < 1 || T > (1 << 24) || batch < 1 || pose0 < 0 || n < 0 || n > batch - pose0 || pose_floats < 1 ||
+        (n > 0 && !e && !t))
+        return DPK_E_INVALID;
+    if (n == 0) return DPK_OK;
+    const long long ne = e ? (long long)n * pose_floats : 0, nt = t ? n : 0;
+    // one work item per float; a grid-stride loop past 2^20 workgroups
+    const long long blocks = std::min<long long>((ne + nt + 255) / 256, 1 << 20);
+    hipLaunchKernelGGL(dpkg::train_draws, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, e, t, ne, nt,
+                       (long long)pose0 * pose_floats, (long long)pose0, (long long)batch, T,
+                       (unsigned long long)e_seed, (unsigned long long)t_seed);
     return hipGetLastError() == hipSuccess ? DPK_OK : DPK_E_HIP;
 }
 

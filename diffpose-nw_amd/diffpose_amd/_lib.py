@@ -17,7 +17,7 @@ ERRORS = {-1: "DPK_E_INVALID", -2: "DPK_E_UNSUPPORTED", -3: "DPK_E_HIP", -4: "DP
 
 # every symbol include/diffpose_kernels.h declares
 EXPORTS = ("dpk_version", "dpk_create", "dpk_set_graph", "dpk_load_weights", "dpk_set_mask", "dpk_set_pose_masks",
-           "dpk_set_schedule", "dpk_eps", "dpk_sample", "dpk_sample_noise", "dpk_sample_start", "dpk_q_sample", "dpk_diff_loss", "dpk_diff_loss_grad", "dpk_diff_loss_grad_train", "dpk_dropout_mask",
+           "dpk_set_schedule", "dpk_eps", "dpk_sample", "dpk_sample_noise", "dpk_sample_start", "dpk_q_sample", "dpk_diff_loss", "dpk_diff_loss_grad", "dpk_diff_loss_grad_train", "dpk_dropout_mask", "dpk_train_draws",
            "dpk_param_count", "dpk_param_layout", "dpk_train_begin", "dpk_train_apply", "dpk_train_sync", "dpk_train_get",
            "dpk_train_set", "dpk_train_end", "dpk_ddim_update", "dpk_ddim_update_noise",
            "dpk_pose", "dpk_pose_metrics", "dpk_pose_metrics_n", "dpk_gmm_sample", "dpk_gmm_sample_f64", "dpk_gmm_sample_n",
@@ -94,6 +94,7 @@ def lib() -> ctypes.CDLL:
     L.dpk_diff_loss_grad_train.argtypes = [vp, vp, vp, vp, i32, vp, u64, ctypes.c_float, ctypes.POINTER(DpkDropout), u64, i64,
                                            vp, vp, i32, vp]
     L.dpk_dropout_mask.argtypes = [u64, i32, i32, ctypes.c_float, i64, i64, vp, vp]
+    L.dpk_train_draws.argtypes = [u64, u64, i32, i64, i64, i32, i32, vp, vp, vp]
     L.dpk_param_count.argtypes = [vp]
     L.dpk_param_layout.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(i64), ctypes.POINTER(i64)]
     L.dpk_train_begin.argtypes = [vp, ctypes.POINTER(DpkOptimConfig)]

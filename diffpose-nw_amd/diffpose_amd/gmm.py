@@ -13,7 +13,9 @@ Random stream: by default the uniforms come from numpy's global RandomState in t
 reference's ``__getitem__`` consumes them (frame by frame, joint by joint; ``choice`` draws one
 ``random_sample()`` per call), so a seeded run selects exactly the components the reference
 selects.  ``seed=`` uses counter-based uniforms generated on the device instead (same
-distribution, no host RNG work; not numpy's stream).
+distribution, no host RNG work; not numpy's stream).  ``batch_device(idx_dev, seed)`` is that seeded call with nothing
+read back: the two device tensors a training step needs, the status word accumulated on the device
+(``check_status()``).
 """
 from __future__ import annotations
 
@@ -62,6 +64,7 @@ class PoseGeneratorGMM:
         self._gmm = torch.from_numpy(np.ascontiguousarray(g, dtype=dt)).to(self.device)
         self._p3 = torch.from_numpy(np.ascontiguousarray(p3, dtype=dt)).to(self.device)
         self._status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._status_acc = torch.zeros(1, dtype=torch.int32, device=self.device)     # batch_device's calls, OR-ed
 
     def __len__(self):
         return len(self._actions)
@@ -91,22 +94,56 @@ class PoseGeneratorGMM:
                 u_ptr, s = u_d.data_ptr(), 0
             else:
                 u_ptr, s = None, int(seed) & 0xFFFFFFFFFFFFFFFF
-            st = torch.cuda.current_stream(self.device) if stream is None else stream
-            name = "dpk_gmm_sample" + ("_f64" if self._f64 else "") + ("" if J == 17 else "_n")
-            head = (self._gmm.data_ptr(), self._p3.data_ptr(), self._gmm.shape[0]) + (() if J == 17 else (J,))
-            rc = getattr(_lib.lib(), name)(*head, self._kernel_n, idx_d.data_ptr(), F, u_ptr, s, self.atol,
-                                           uv.data_ptr(), ns.data_ptr(), self._status.data_ptr(),
-                                           ctypes.c_void_p(st.cuda_stream))
-            _lib.check(None, name, rc)
-            flags = int(self._status.item())
-            if flags & 1:
-                raise ValueError("probabilities are not non-negative")
-            if flags & 2:
-                raise ValueError("probabilities do not sum to 1")
+            self._launch(idx_d, F, u_ptr, s, uv, ns, stream)
+            self._raise(int(self._status.item()))
         srcs = [self._src(i) for i in idx]
         actions = [self._actions[i] for i in srcs]
         cam = torch.from_numpy(self._camerapara[srcs].astype(np.float32)) if F else None
         return uv, ns, uv[..., :2], uv[..., 2:], actions, cam
+
+    def _launch(self, idx_d, F, u_ptr, s, uv, ns, stream):
+        """The ``dpk_gmm_sample*`` call of this dataset's dtype and joint count; its status word lands in ``_status``."""
+        J = self.n_pts
+        st = torch.cuda.current_stream(self.device) if stream is None else stream
+        name = "dpk_gmm_sample" + ("_f64" if self._f64 else "") + ("" if J == 17 else "_n")
+        head = (self._gmm.data_ptr(), self._p3.data_ptr(), self._gmm.shape[0]) + (() if J == 17 else (J,))
+        rc = getattr(_lib.lib(), name)(*head, self._kernel_n, idx_d.data_ptr(), F, u_ptr, s, self.atol,
+                                       uv.data_ptr(), ns.data_ptr(), self._status.data_ptr(),
+                                       ctypes.c_void_p(st.cuda_stream))
+        _lib.check(None, name, rc)
+
+    @staticmethod
+    def _raise(flags: int) -> None:
+        if flags & 1:
+            raise ValueError("probabilities are not non-negative")
+        if flags & 2:
+            raise ValueError("probabilities do not sum to 1")
+
+    def batch_device(self, idx_dev, seed, stream=None):
+        """The wait-free sibling of ``batch(indices, seed=seed)``: ``idx_dev`` an int64 tensor of frame indices on this
+        dataset's device, the same ``dpk_gmm_sample*`` call under ``seed``; returns ``(uvxyz [F,J,5], noise_scale
+        [F,J,5])`` device tensors, bitwise ``batch``'s first two, and nothing from the host (no actions, no camera
+        parameters).  The call's status word is OR-ed into a device accumulator instead of being read:
+        ``check_status()`` reads it later.  On ``stream`` (default: the current stream), as the accumulation is."""
+        if not (torch.is_tensor(idx_dev) and idx_dev.dtype == torch.int64 and idx_dev.device == self._gmm.device):
+            raise ValueError(f"idx_dev must be an int64 tensor on {self.device}")
+        idx_d = idx_dev.reshape(-1).contiguous()
+        F, J = idx_d.numel(), self.n_pts
+        uv = torch.empty(F, J, 5, dtype=torch.float32, device=self.device)
+        ns = torch.empty(F, J, 5, dtype=torch.float32, device=self.device)
+        if F:
+            st = torch.cuda.current_stream(self.device) if stream is None else stream
+            with torch.cuda.stream(st):
+                self._launch(idx_d, F, None, int(seed) & 0xFFFFFFFFFFFFFFFF, uv, ns, st)
+                self._status_acc |= self._status
+        return uv, ns
+
+    def check_status(self) -> None:
+        """Read and clear the status accumulated by ``batch_device`` (one wait for the device) and raise numpy's
+        ValueError for a negative weight or for weights that do not sum to 1, as ``batch`` does per call."""
+        flags = int(self._status_acc.item())
+        self._status_acc.zero_()
+        self._raise(flags)
 
     def __getitem__(self, index):
         """One frame, as the reference's ``__getitem__`` returns it (CPU tensors)."""

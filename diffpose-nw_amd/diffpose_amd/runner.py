@@ -9,6 +9,7 @@ Mirrors ``Diffpose`` in ``runners/diffpose_frame.py``:
 | ``create_pose_model`` | 134-154 | ``HipGCNpose`` handle, optional checkpoint |
 | ``test_hyber`` | 270-420 | pose front-end plus uvxyz assembly (one launch); the K-step DDIM sampler (one launch); per-frame MPJPE / P-MPJPE (one launch); the reference's per-action accounting on the host. Returns (p1, p2) in mm |
 | ``train_step`` | 211-233 for one batch | draws, the per-pose losses and every parameter's gradient in one ``dpk_diff_loss_grad`` call (eval mode), ``.grad`` on the caller's torch parameters, clipping, ``optimizer.step()``, the weights loaded back. Returns ``loss_diff`` |
+| ``train`` | 156-268 | the run on a ``DeviceAdam``: per epoch the shuffle, one wait-free step per batch (``PoseGeneratorGMM.batch_device``, ``dpk_train_draws``, the gradient call, ``optimizer.step``), ``lr_decay``, the reference's checkpoint list, ``test_hyber(is_train=True)``; ``resume=``; data-parallel under torch.distributed. Returns (best_epoch, best_p1) |
 | ``diffusion_loss`` | 203-233, forward only | the training objective in eval mode: per-pose-t noising, eps and the per-pose sums in one ``dpk_diff_loss`` call per batch; the reference's ``update(loss_diff, n)`` on the host. Returns the epoch average |
 
 Several ranks (``torch.distributed`` initialised with world size > 1, one process per GPU): every
@@ -405,12 +406,7 @@ class Diffpose:
         losses (float32 [B] on the device) instead of their mean as a float, which costs a wait for the device."""
         from .schedule import training_timesteps
 
-        p_drop = float(getattr(self.config.model, "dropout", 0.0) or 0.0)
-        train_dropout = bool(getattr(self.args, "train_dropout", False))
-        if p_drop != 0.0 and not train_dropout and not getattr(self.args, "train_without_dropout", False):
-            raise NotImplementedError(f"config.model.dropout = {p_drop}: the device backward runs without dropout masks "
-                                      "by default; set args.train_dropout to train with dropout as the reference does, "
-                                      "args.train_without_dropout to train in eval mode, or dropout to 0")
+        train_dropout = self._dropout_mode()
         x0 = torch.as_tensor(targets_uvxyz).detach().to(torch.float32)
         noise_scale = torch.as_tensor(noise_scale).detach().to(torch.float32)
         B = x0.shape[0]
@@ -461,6 +457,181 @@ class Diffpose:
             epoch.update(float(losses.cpu().mean()), losses.numel())
         self.epoch_loss_diff = epoch.avg
         return epoch.avg
+
+    def _dropout_mode(self) -> bool:
+        """``train_step``'s rule: True for the train-mode step (``args.train_dropout``), False for eval-mode gradients;
+        a config with dropout and neither flag raises."""
+        p_drop = float(getattr(self.config.model, "dropout", 0.0) or 0.0)
+        train_dropout = bool(getattr(self.args, "train_dropout", False))
+        if p_drop != 0.0 and not train_dropout and not getattr(self.args, "train_without_dropout", False):
+            raise NotImplementedError(f"config.model.dropout = {p_drop}: the device backward runs without dropout masks "
+                                      "by default; set args.train_dropout to train with dropout as the reference does, "
+                                      "args.train_without_dropout to train in eval mode, or dropout to 0")
+        return train_dropout
+
+    def train_draws(self, e_seed: int, t_seed: int, B: int, lo: int = 0, hi=None, stream=None):
+        """``dpk_train_draws`` for poses ``lo .. hi - 1`` of a batch of ``B``: ``(e [hi - lo, n_pts, 5], t [hi - lo])``
+        float32 device tensors, each value a function of its seed and its global index alone (a shard's rows are
+        bitwise the whole batch's rows).  ``e`` is what the loss calls draw for ``noise=None`` under ``seed=e_seed``;
+        ``t`` the reference's antithetic pair draw (runners/diffpose_frame.py:216-218)."""
+        import ctypes
+
+        from . import _lib
+
+        hi = B if hi is None else hi
+        n = hi - lo
+        e = torch.empty((n, self.n_pts, 5), dtype=torch.float32, device=self.device)
+        t = torch.empty(n, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            st = torch.cuda.current_stream(self.device) if stream is None else stream
+            rc = _lib.lib().dpk_train_draws(ctypes.c_uint64(e_seed & (2 ** 64 - 1)), ctypes.c_uint64(t_seed & (2 ** 64 - 1)),
+                                            int(self.num_timesteps), int(B), int(lo), int(n), self.n_pts * 5,
+                                            e.data_ptr() if n else None, t.data_ptr() if n else None, st.cuda_stream)
+        if rc:
+            raise _lib.DpkError("dpk_train_draws", rc, f"T {self.num_timesteps} batch {B} pose0 {lo} n {n}")
+        return e, t
+
+    def _host_betas(self):
+        """``self.betas`` as a host array, read back once: a gradient call given it does not wait for the device"""
+        if getattr(self, "_betas_host", None) is None:
+            self._betas_host = np.ascontiguousarray(self.betas.cpu().numpy(), dtype=np.float32)
+        return self._betas_host
+
+    def _step_grads(self, train_data, rows, lo, hi, B, seeds, dropout):
+        """The device part of one step of ``train`` for this rank's poses ``lo .. hi - 1`` of the batch ``rows``: the
+        whole batch's GMM draw (its uniforms are keyed by the output position) and its rows, this shard's e and t,
+        the gradient call with weight 1 / B.  Returns (the shard's loss sum, a float64 0-d device tensor; the flat
+        gradient).  Nothing here waits for the device."""
+        gmm_seed, e_seed, t_seed, drop_seed = seeds
+        uvxyz, scale = train_data.batch_device(rows, gmm_seed)
+        e, t = self.train_draws(e_seed, t_seed, B, lo, hi)
+        drop = dict(dropout=True, dropout_seed=drop_seed) if dropout else {}
+        loss, grads = self.model_diff.diffusion_loss_grad(uvxyz[lo:hi], t, self._host_betas(), noise_scale=scale[lo:hi],
+                                                          noise=e, mask=self.src_mask, weight=1.0 / B, pose0=lo, **drop)
+        return loss.sum(dtype=torch.float64), grads.flat
+
+    def _train_inner(self, train_data, optimizer, epoch: int, step: int, step_grads=None, dropout: bool = False):
+        """The inner loop of epoch ``epoch`` of ``train`` from global step ``step``: the epoch's permutation (one upload),
+        then per batch the device part of the step, the all-reduce of the gradient where there are several ranks and
+        ``optimizer.step``.  Returns (the global step after the epoch, this rank's loss sum per batch as a float64
+        device tensor, the batch sizes).  Waits for the device only at the reference's ``i % 100`` log line."""
+        from .schedule import train_epoch_permutation, train_step_seeds
+
+        world, rank, distributed = self._world()
+        bs, n_data = int(self.config.training.batch_size), len(train_data)
+        perm = train_epoch_permutation(self.args.seed, epoch, n_data).to(self.device)     # one upload per epoch
+        n_batches = (n_data + bs - 1) // bs
+        slots = torch.zeros(n_batches, dtype=torch.float64, device=self.device)
+        sizes, seen = [], 0
+        for i in range(n_batches):
+            step += 1
+            rows = perm[i * bs:(i + 1) * bs]
+            B = int(rows.numel())
+            lo, hi = shard_frames(B, world, rank)
+            seeds = train_step_seeds(self.args.seed, step)
+            if step_grads is not None:
+                loss_sum, flat = step_grads(rows, lo, hi, B, seeds)
+            else:
+                loss_sum, flat = self._step_grads(train_data, rows, lo, hi, B, seeds, dropout)
+            if distributed:
+                dist.all_reduce(flat, op=dist.ReduceOp.SUM)
+            optimizer.step(flat)
+            slots[i] = loss_sum
+            sizes.append(B)
+            seen += hi - lo
+            if i % 100 == 0 and i != 0:
+                logging.info("| Epoch%04d: %04d/%04d | Step %06d | Loss: %.6f |", epoch, i + 1, n_batches, step,
+                             float(slots[:i + 1].sum()) / max(seen, 1))
+        return step, slots, sizes
+
+    def train(self, train_data, eval_batches=None, resume=None, *, optimizer=None, step_grads=None, frame_errors=None):
+        """The reference's training run (runners/diffpose_frame.py:156-268) on the device-side step: for
+        ``config.training.n_epochs`` epochs, shuffle ``train_data`` (a ``PoseGeneratorGMM`` on this runner's device),
+        take one clip + Adam + EMA step per batch of ``config.training.batch_size`` frames (the last, partial batch
+        kept), then decay the learning rate (``config.optim.{lr, decay, lr_gamma}``, common/utils.py:26-30), write the
+        reference's checkpoint to ``ckpt_{epoch}.pth`` and ``ckpt.pth`` under ``args.log_path`` and evaluate with
+        ``test_hyber(batches=eval_batches, is_train=True)`` (``eval_batches``: an iterable, a callable that returns
+        a fresh one per epoch, or None for ``test_hyber``'s own default).  Returns ``(best_epoch, best_p1)``, kept as
+        ``self.best_epoch``, ``self.best_p1``; every epoch's loss average (the reference's ``AverageMeter`` over
+        ``update(loss_diff, B)``) is ``self.epoch_loss_diff``, all of them ``self.train_log``.
+
+        The optimiser is ``model_diff.device_optimizer(config)`` (Adam; RMSProp and SGD raise there), opened here unless
+        one is already open on the model or given as ``optimizer``, and left open on return.  Dropout follows
+        ``train_step``'s rule (``args.train_dropout`` / ``args.train_without_dropout``).
+
+        Every draw is a function of ``(args.seed, epoch, step)`` (``schedule.word``): the 1-based global step s uses
+        words 4 s .. 4 s + 3 as the GMM seed, e's seed, t's seed and the dropout seed; epoch ep shuffles with
+        ``schedule.train_epoch_permutation``.  No generator state lives elsewhere, so ``resume=path`` (a checkpoint
+        written here or by the reference: parameters, Adam state, epoch, step and the EMA shadow when present)
+        continues the uninterrupted run exactly, except that ``best_p1`` is not in the reference's format and
+        restarts at 1000.
+
+        Several ranks (an initialised torch.distributed job): every rank draws the whole batch's GMM sample and runs
+        the poses ``shard_frames(B, world, rank)`` with weight 1 / B and the batch's own rows of e, t and the dropout
+        masks (``dpk_train_draws``, ``pose0``); one all-reduce of the flat gradient per step, and every rank applies
+        the same bits with the deterministic ``dpk_train_apply``, so the parameters stay bitwise equal without a
+        broadcast.  One more all-reduce per epoch sums the per-batch loss slots.  Rank 0 writes the files.
+
+        The inner loop does not wait for the device except at the reference's ``i % 100`` log line, which reads this
+        rank's losses so far.  ``step_grads`` replaces the device part of a step (tests of the loop, the sharding, the
+        collectives, the schedule and the checkpoints on the CPU): ``fn(rows, lo, hi, B, seeds) -> (loss sum of the
+        rank's poses, flat gradient)`` with ``rows`` the batch's int64 frame indices on the runner's device and
+        ``seeds`` the step's four; ``frame_errors`` is passed on to ``test_hyber``."""
+        cfg, args = self.config, self.args
+        if optimizer is None:
+            optimizer = getattr(self.model_diff, "_trainer", None) or self.model_diff.device_optimizer(cfg)
+        dropout = self._dropout_mode() if step_grads is None else False
+        world, rank, distributed = self._world()
+        lr_init, decay, gamma = cfg.optim.lr, cfg.optim.decay, cfg.optim.lr_gamma
+        ema = bool(getattr(cfg.model, "ema", False))
+        log_path = getattr(args, "log_path", None)
+        best_p1, best_epoch = 1000, 0
+        start_epoch, step = 0, 0
+        if resume is not None:
+            states = torch.load(resume, map_location="cpu", weights_only=True)
+            optimizer.load_params(states[0])
+            optimizer.load_state_dict(states[1])
+            if len(states) > 4:
+                optimizer.load_ema_state_dict(states[4])
+            start_epoch, step = int(states[2]) + 1, int(states[3])
+        self.train_log = []
+        for epoch in range(start_epoch, int(cfg.training.n_epochs)):
+            step, slots, sizes = self._train_inner(train_data, optimizer, epoch, step, step_grads, dropout)
+            if distributed:
+                dist.all_reduce(slots, op=dist.ReduceOp.SUM)
+            meter = metrics.AverageMeter()
+            for total, B in zip(slots.cpu().tolist(), sizes):
+                meter.update(total / B, B)                                    # :233 with loss_diff = the batch mean
+            self.epoch_loss_diff = meter.avg
+            if epoch % decay == 0:
+                lr_now = lr_init * gamma ** (epoch / decay)                   # common/utils.py:26-30
+                for group in optimizer.param_groups:
+                    group["lr"] = lr_now
+            train_data.check_status()
+            if rank == 0 and log_path:
+                from collections import OrderedDict
+
+                states = [OrderedDict(("module." + k, v.detach().cpu().clone())
+                                      for k, v in optimizer.params_state_dict().items()),
+                          optimizer.state_dict(), epoch, step]
+                if ema:
+                    states.append(OrderedDict((k, v.detach().cpu().clone())
+                                              for k, v in optimizer.ema_state_dict().items()))
+                os.makedirs(log_path, exist_ok=True)
+                torch.save(states, os.path.join(log_path, f"ckpt_{epoch}.pth"))
+                torch.save(states, os.path.join(log_path, "ckpt.pth"))
+            logging.info("test the performance of current model")
+            kw = {} if frame_errors is None else {"frame_errors": frame_errors}
+            p1, p2 = self.test_hyber(batches=eval_batches() if callable(eval_batches) else eval_batches, is_train=True,
+                                     **kw)
+            if p1 < best_p1:
+                best_p1, best_epoch = p1, epoch
+            logging.info("| Best Epoch: %04d MPJPE: %.2f | Epoch: %04d MPJEPE: %.2f PA-MPJPE: %.2f |", best_epoch,
+                         best_p1, epoch, p1, p2)
+            self.train_log.append(dict(epoch=epoch, step=step, loss_diff=self.epoch_loss_diff, p1=p1, p2=p2,
+                                       lr=float(optimizer.param_groups[0]["lr"])))
+        self.best_p1, self.best_epoch = best_p1, best_epoch
+        return best_epoch, best_p1
 
     def log_performance_metrics(self, output_path=None):
         """Summary of the per-batch inference times and peak-memory deltas collected under

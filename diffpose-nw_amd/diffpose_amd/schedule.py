@@ -79,6 +79,32 @@ def training_timesteps(n: int, T: int, generator=None):
     return torch.cat([t, T - t - 1], dim=0)[:n]
 
 
+def word(seed: int, ctr: int) -> int:
+    """The 64-bit counter-based word of the library's seeded draws (csrc/dpk_counter.inc): splitmix64's output mixer
+    on ``seed + 0x9E3779B97F4A7C15 * (ctr + 1)`` mod 2^64.  ``runner.Diffpose.train`` derives every seed of a run
+    from ``word(args.seed, counter)``."""
+    m = (1 << 64) - 1
+    z = (int(seed) + 0x9E3779B97F4A7C15 * (int(ctr) + 1)) & m
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+    return z ^ (z >> 31)
+
+
+def train_step_seeds(run_seed: int, step: int):
+    """(GMM seed, e_seed, t_seed, dropout seed) of the 1-based global ``step`` of a training run: words 4 s .. 4 s + 3
+    of ``run_seed``."""
+    return tuple(word(run_seed, 4 * int(step) + k) for k in range(4))
+
+
+def train_epoch_permutation(run_seed: int, epoch: int, n: int):
+    """The shuffle of epoch ``epoch``: torch.randperm(n) under a CPU generator seeded with word(run_seed, 2^62 + epoch)
+    (63 bits), an int64 CPU tensor."""
+    import torch
+
+    g = torch.Generator().manual_seed(word(run_seed, 2 ** 62 + int(epoch)) & (2 ** 63 - 1))
+    return torch.randperm(int(n), generator=g)
+
+
 def step_pairs(seq):
     """(t, next_t) in execution order (common/utils_diff.py:49-52)."""
     seq = list(seq)

@@ -296,6 +296,28 @@ int dpk_diff_loss_grad_train(dpk_handle* h, const float* x0_dev, const float* t_
  * [0, 1), negative first or n, or a NULL keep_dev with n > 0. */
 int dpk_dropout_mask(uint64_t drop_seed, int layer, int site, float p, int64_t first, int64_t n, uint8_t* keep_dev,
                      void* stream);
+/* The draws of one training step (runners/diffpose_frame.py:214-218) without a handle: e and the antithetic t of poses
+ * pose0 .. pose0 + n - 1 of a global batch of `batch` poses, every value a function of its seed and its global index
+ * alone, so a rank's rows are bitwise the rows of the whole batch's draw.  These formulas are the contract.
+ *   e_dev [n,pose_floats] or NULL.  For global pose p = pose0 .. pose0 + n - 1 and element r of it,
+ *             e_dev[(p - pose0) * pose_floats + r] = normal_noise(e_seed, step = -1, idx = p * pose_floats + r),
+ *         the draw of the sampler and the loss calls: Philox4x32-10 at counter {idx lo, idx hi, 0xFFFFFFFF, 0x5EED}
+ *         under the key {e_seed lo, e_seed hi}, u1 = ((c0 >> 8) + 1) / 2^24, u2 = (c1 >> 8) / 2^24,
+ *         z = sqrtf(-2 logf(u1)) * cosf(6.283185307179586f * u2) in fp32.  idx is 64-bit, both counter words are live.
+ *         At pose0 = 0 it is bitwise what dpk_diff_loss, dpk_diff_loss_grad(_train) and dpk_q_sample draw for a NULL
+ *         noise_dev under seed = e_seed; a shard passes its rows as noise_dev.
+ *   t_dev [n] or NULL: float, integer-valued, the array dpk_diff_loss_grad takes.  The reference's
+ *         cat([r, T - r - 1])[:batch] of h = batch / 2 + 1 draws r: with q = p < h ? p : p - h (p - h < h always),
+ *             w = splitmix64's output mixer on t_seed + 0x9E3779B97F4A7C15 * (q + 1) mod 2^64
+ *                 (the 64-bit word behind dpk_gmm_sample's seeded uniforms at counter q),
+ *             r = ((w >> 32) * T) >> 32,        t = p < h ? r : T - 1 - r,
+ *         integer arithmetic only; T = the number of diffusion timesteps, t in 0 .. T - 1.
+ * One elementwise launch on `stream` of the current device.  The caller-memory contract above: exactly n * pose_floats
+ * and n floats written, pointers 4-byte aligned, a NULL output untouched, n = 0 returns DPK_OK and touches nothing;
+ * capture-safe (nothing allocated, every scalar passed by value).  DPK_E_INVALID, before anything is touched, for T < 1 or
+ * T > 2^24, batch < 1, pose0 < 0, n < 0, pose0 + n > batch, pose_floats < 1, or both outputs NULL with n > 0. */
+int dpk_train_draws(uint64_t e_seed, uint64_t t_seed, int T, int64_t batch, int64_t pose0, int n, int pose_floats,
+                    float* e_dev, float* t_dev, void* stream);
 /* Parameters of a GCNdiff handle (0 for NULL or a GCNpose handle), and entry i of their layout in grads_dev. */
 int dpk_param_count(const dpk_handle* h);
 int dpk_param_layout(const dpk_handle* h, int i, const char** name, int64_t* offset, int64_t* numel);
